@@ -17,7 +17,14 @@ loss bookkeeping; the timed region ends with the flush that makes every row curr
 Inputs are resident in HBM before the timed region; the walk and grouping of every
 timed step run inside it.
 
-Prints ONE JSON line (rank 0). With --gpus N>1 (torchrun, one rank per GPU) the
+A plain run sets up, warms up, times the --steps steps and prints ONE JSON line (rank 0):
+the headline figure and `ms_per_step`. --dump-outputs DIR also writes what the timed steps
+computed (both tables after the closing flush, the per-step losses) as DIR/<name>.npy.
+--full adds every other leg to the line, each a run of its own after the timed region: the
+per-kernel event window and its rooflines, the full-sort evaluation, the K3 gather roofline
+and the CPU baseline (--no-eval / --no-cpu-baseline leave legs out of a --full run).
+
+With --gpus N>1 (torchrun, one rank per GPU) the
 tables are ROW-SHARDED (cyclic ownership; --dp-mode replicated keeps
 replicas): each optimizer step consumes a global batch of N x 512 positives, every
 rank walks and groups the global batch, owners send the rows each rank's slice reads
@@ -489,6 +496,32 @@ def cpu_baseline(train, step_obj, d, neg, steps, warmup=20, runs=3):
                       f'dense Adam; {sum(dts):.1f} s timed in all'}
 
 
+DUMP_MAX_BYTES = 48 << 20     # all dumped arrays together stay below 64 MB
+
+
+def dump_outputs(out_dir, step, W, K, seed=0):
+    """What the timed steps leave their caller, as float32 `<name>.npy` files in out_dir:
+    both embedding tables after the closing flush (every row current) and the per-step mean
+    losses of the K timed steps. Called right after the timed region (before anything else
+    advances the tables). A table that does not fit the budget is written as a fixed sample
+    of its rows: a seeded draw without replacement, ascending, the same for the same table
+    shape and seed."""
+    os.makedirs(out_dir, exist_ok=True)
+    tables = {'user_embedding': step.pU.detach(), 'item_embedding': step.pI.detach()}
+    budget = DUMP_MAX_BYTES
+    for name, t in sorted(tables.items(), key=lambda kv: kv[1].numel()):   # small ones whole
+        rows = t.shape[0]
+        fit = max(budget // (t.shape[1] * 4), 1)
+        if rows > fit:
+            idx = np.sort(np.random.default_rng(seed).choice(rows, fit, replace=False))
+            t = t[torch.as_tensor(idx, device=t.device)]
+        a = t.to(torch.float32).cpu().numpy()
+        budget -= a.nbytes
+        np.save(os.path.join(out_dir, f'{name}.npy'), a)
+    loss = step.loss_hist[W:W + K].to(torch.float32).cpu().numpy()
+    np.save(os.path.join(out_dir, 'loss.npy'), loss)
+
+
 def _spawn_ranks(n):
     """`--gpus N` without a torchrun environment: start N ranks (one process per
     GPU) with torch.distributed.run and exit with its status. This parent never
@@ -511,9 +544,16 @@ def main():
     # sampler walk + grouping of every timed step, see below)
     ap.add_argument('--steps', type=int, default=256)
     ap.add_argument('--warmup', type=int, default=64)
+    # everything beside the headline figure (the per-kernel event window and its rooflines,
+    # the full-sort evaluation, the K3 gather roofline, the CPU baseline) runs with --full only
+    ap.add_argument('--full', action='store_true')
+    # write what the timed steps computed (tables after the closing flush, per-step losses)
+    # as DIR/<name>.npy (float32; rank 0's arrays)
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None)
     ap.add_argument('--cpu-steps', type=int, default=200)
     ap.add_argument('--cpu-warmup', type=int, default=20)
     ap.add_argument('--cpu-runs', type=int, default=3)
+    # with --full: leave the CPU baseline / the evaluation and gather legs out
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-eval', action='store_true')
     ap.add_argument('--adam-mode', default='deferred', choices=['deferred', 'streamed'])
@@ -602,7 +642,9 @@ def main():
     # until the timed region has started: the timed region holds the K4 walk and the
     # K2 grouping of every timed step (the first timed chunk's serially, the rest on
     # the prep stream beside the model side, as in steady state).
-    M = step.C                                 # per-kernel measurement window after it
+    # per-kernel measurement window after it (run with --full only; the plan is cut the
+    # same way without it, so the timed steps are the same steps in both)
+    M = step.C
     # every row complete at the end of the timed region and of the measurement window
     nb = step.begin_epoch(cuts=(W, W + K, W + K + M), hold_prep_from=W,
                           flush_at=(W + K, W + K + M))
@@ -635,24 +677,32 @@ def main():
         tdist.all_reduce(t, op=tdist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    # Per-kernel HIP events around each model-side launch, on the stream it runs
-    # on, over M further steps launched eagerly behind a spin kernel so the
-    # events bracket kernel time only (not host enqueue gaps).
-    # spin long enough (~2.4k cycles/us) to cover the host's enqueue of the whole
-    # window (~5 eager launches per step), so the events bracket kernel time only
-    step.release_prep()
-    torch.cuda._sleep(int(2.4e3 * 400 * M))
-    step.kernel_events, step.kernel_uniq = [], []
-    step.run_batches(W + K, W + K + M)
-    torch.cuda.synchronize()
-    events, uniq = step.kernel_events, step.kernel_uniq
-    step.kernel_events = None
-    losses = step.end_epoch(W + K + M)
-    assert all(np.isfinite(losses)), 'non-finite loss'
-    roof, roof_bpr, kernels_us = roofline(step, events, uniq, d, M, W, K)
-    mine = {'rank': rank, 'timed_s': round(local_elapsed, 6), 'kernels_us': kernels_us,
-            'k5_us_per_step': roof.get('us_per_step', roof.get('valu', {}).get('us_per_step')),
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step, W, K)
+
+    mine = {'rank': rank, 'timed_s': round(local_elapsed, 6),
             'table_rows': int(getattr(step, 'SU', step.nU) + getattr(step, 'SI', step.nI))}
+    roof = roof_bpr = kernels_us = None
+    if args.full:
+        # Per-kernel HIP events around each model-side launch, on the stream it runs
+        # on, over M further steps launched eagerly behind a spin kernel so the
+        # events bracket kernel time only (not host enqueue gaps).
+        # spin long enough (~2.4k cycles/us) to cover the host's enqueue of the whole
+        # window (~5 eager launches per step), so the events bracket kernel time only
+        step.release_prep()
+        torch.cuda._sleep(int(2.4e3 * 400 * M))
+        step.kernel_events, step.kernel_uniq = [], []
+        step.run_batches(W + K, W + K + M)
+        torch.cuda.synchronize()
+        events, uniq = step.kernel_events, step.kernel_uniq
+        step.kernel_events = None
+        losses = step.end_epoch(W + K + M)
+        roof, roof_bpr, kernels_us = roofline(step, events, uniq, d, M, W, K)
+        mine.update({'kernels_us': kernels_us, 'k5_us_per_step': roof.get(
+            'us_per_step', roof.get('valu', {}).get('us_per_step'))})
+    else:
+        losses = step.end_epoch(W + K)
+    assert all(np.isfinite(losses)), 'non-finite loss'
     per_rank = [mine]
     if dist:
         per_rank = [None] * world
@@ -692,9 +742,6 @@ def main():
                                'alias table (NON-PARITY fast mode)'),
                    'chunk_plan_timed': [n for b0, n, _ in step._plan if W <= b0 < W + K],
                    'eager_steps_timed': eager_timed},
-        'roofline': roof,
-        'roofline_bpr': roof_bpr,
-        'kernels_us': kernels_us,
         'ranks': per_rank,
         'adam_mode': step.adam_mode,
         'fused_step': bool(getattr(step, 'fused_step', False)),
@@ -702,7 +749,9 @@ def main():
         'setup_s': round(setup_s, 1),
         'setup': step.setup_info,
     }
-    if not args.no_eval and rank == 0:
+    if args.full:
+        result.update({'roofline': roof, 'roofline_bpr': roof_bpr, 'kernels_us': kernels_us})
+    if args.full and not args.no_eval and rank == 0:
         from recbole_amd.trainer.fused import fused_full_sort_eval
         from recbole_amd.evaluator import TopKEvaluator
         ev = TopKEvaluator(config, ['recall', 'mrr', 'ndcg', 'hit', 'precision'])
@@ -735,9 +784,9 @@ def main():
                               'end_to_end_frac': round(flops / e_dt / 1e12 / VALU_PEAK_TFLOPS, 4),
                               'flops_formula': '2 * n_items * d per user (the score matmul)',
                               'timing': 'HIP events around each K6 launch on its stream'}}
-    if rank == 0 and not args.no_eval:
+    if args.full and rank == 0 and not args.no_eval:
         result['gather_throughput'] = gather_throughput(step, d, neg)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result['cpu_baseline'] = cpu_baseline(train, step, d, neg, args.cpu_steps,
                                               args.cpu_warmup, args.cpu_runs)
     if rank == 0:

@@ -7,7 +7,7 @@
 # crash / fault / timeout must not be followed by more GPU work). Tasks:
 #   smoke            __graft_entry__.smoke()
 #   tests[:ARGS]     pytest -m gpu (ARGS: test files / -k, ':'-separated words -> spaces)
-#   drv[:N]          N driver-window bench lines (--warmup 5 --steps 20), default 3
+#   drv[:N]          N driver-window bench lines (--full --warmup 5 --steps 20, no eval / CPU legs), default 3
 #   def[:N]          N default-window bench lines (64 + 256 steps), default 1
 #   full             one driver-window bench with eval + gather + CPU baseline (BENCH line)
 #   trace            kernel + HIP runtime trace of the driver window (tools/trace_short.sh)
@@ -54,35 +54,35 @@ for task in "$@"; do
       say "tests: $(tail -1 $O/tests.log)";;
     drv)
       for i in $(seq 1 ${arg:-3}); do
-        run drv_$i 300 python bench.py --warmup 5 --steps 20 --no-cpu-baseline --no-eval ${BENCH_ARGS:-}
+        run drv_$i 300 python bench.py --full --warmup 5 --steps 20 --no-cpu-baseline --no-eval ${BENCH_ARGS:-}
         say "drv $i: $(line $O/drv_$i.log)"
       done;;
     def)
       for i in $(seq 1 ${arg:-1}); do
-        run def_$i 400 python bench.py --no-cpu-baseline --no-eval ${BENCH_ARGS:-}
+        run def_$i 400 python bench.py --full --no-cpu-baseline --no-eval ${BENCH_ARGS:-}
         say "def $i: $(line $O/def_$i.log)"
       done;;
     full)
-      run full 600 python bench.py --warmup 5 --steps 20 ${BENCH_ARGS:-}
+      run full 600 python bench.py --full --warmup 5 --steps 20 ${BENCH_ARGS:-}
       say "full: $(line $O/full.log)";;
     trace)
       rm -rf "$O/trace"; mkdir -p "$O/trace"
       BENCH_MARKERS=1 run trace 400 rocprofv3 --kernel-trace --hip-runtime-trace --output-format csv \
-        -d "$O/trace" -o run -- python bench.py --warmup 5 --steps 20 --no-cpu-baseline --no-eval \
+        -d "$O/trace" -o run -- python bench.py --full --warmup 5 --steps 20 --no-cpu-baseline --no-eval \
         ${BENCH_ARGS:-}
       python tools/check_timed_window.py "$O/trace" "$O/timed_window.json" > "$O/tw.txt" || exit 4
       say "trace: $(head -3 $O/tw.txt | tr -d '\n')";;
     stats)
       rm -rf "$O/stats"
       run stats 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/stats" -o run -- \
-        python bench.py --warmup 5 --steps 20 --no-cpu-baseline --no-eval ${BENCH_ARGS:-}
+        python bench.py --full --warmup 5 --steps 20 --no-cpu-baseline --no-eval ${BENCH_ARGS:-}
       say "stats: $(line $O/stats.log)";;
     pmc)
       for c in FETCH_SIZE WRITE_SIZE "SQ_INSTS_VALU SQ_INSTS_VALU_TRANS_F32 SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES"; do
         tag=${c%% *}
         rm -rf "$O/pmc_$tag"
         run pmc_$tag 300 rocprofv3 --pmc $c --output-format csv -d "$O/pmc_$tag" -o run -- \
-          python bench.py --warmup 5 --steps 20 --no-cpu-baseline --no-eval ${BENCH_ARGS:-}
+          python bench.py --full --warmup 5 --steps 20 --no-cpu-baseline --no-eval ${BENCH_ARGS:-}
         say "pmc $tag ok"
       done;;
     models)

@@ -57,5 +57,5 @@ def patched(self, slot, c, Bc, stream, step_off, ahead):
 
 
 S._adam_ipc = patched
-sys.argv = ['bench.py', '--gpus', '1', '--dp-mode', 'sharded'] + sys.argv[2:]
+sys.argv = ['bench.py', '--gpus', '1', '--dp-mode', 'sharded', '--full'] + sys.argv[2:]
 bench.main()
