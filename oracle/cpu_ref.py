@@ -612,6 +612,13 @@ def leave_one_out_index(group_keys, leave_one_num):
     return nxt
 
 
+def _drop(x, keep, p):
+    """Dropout with a given boolean keep mask (x's shape): x * keep / (1 - p); keep None: x."""
+    if keep is None:
+        return x
+    return x * torch.as_tensor(keep).reshape(x.shape).to(x.dtype) / (1.0 - p)
+
+
 class _MHA(torch.nn.Module):
     def __init__(self, h, d, eps):
         super().__init__()
@@ -624,14 +631,14 @@ class _MHA(torch.nn.Module):
     def _t(self, x):
         return x.view(*(x.size()[:-1] + (self.h, self.hd))).permute(0, 2, 1, 3)
 
-    def forward(self, x, mask):
+    def forward(self, x, mask, keep_attn=None, p_attn=0.0, keep_out=None, p_hidden=0.0):
         import math
         q, k, v = self._t(self.query(x)), self._t(self.key(x)), self._t(self.value(x))
         sc = torch.matmul(q, k.transpose(-1, -2)) / math.sqrt(self.hd) + mask
-        p = torch.softmax(sc, dim=-1)
+        p = _drop(torch.softmax(sc, dim=-1), keep_attn, p_attn)
         c = torch.matmul(p, v).permute(0, 2, 1, 3).contiguous()
         c = c.view(*(c.size()[:-2] + (self.h * self.hd,)))
-        return self.LayerNorm(self.dense(c) + x)
+        return self.LayerNorm(_drop(self.dense(c), keep_out, p_hidden) + x)
 
 
 class _FF(torch.nn.Module):
@@ -640,11 +647,11 @@ class _FF(torch.nn.Module):
         self.dense_1, self.dense_2 = torch.nn.Linear(d, inner), torch.nn.Linear(inner, d)
         self.LayerNorm = torch.nn.LayerNorm(d, eps=eps)
 
-    def forward(self, x):
+    def forward(self, x, keep=None, p_hidden=0.0):
         import math
         h = self.dense_1(x)
         h = h * 0.5 * (1.0 + torch.erf(h / math.sqrt(2.0)))
-        return self.LayerNorm(self.dense_2(h) + x)
+        return self.LayerNorm(_drop(self.dense_2(h), keep, p_hidden) + x)
 
 
 class _TL(torch.nn.Module):
@@ -655,8 +662,8 @@ class _TL(torch.nn.Module):
 
 
 class SASRecCPU(torch.nn.Module):
-    """SASRec with dropout 0 (the reference's module tree: state_dict keys match),
-    forward / losses as written in sasrec.py:107-158 on torch CPU. loss 'SSM' is
+    """SASRec with dropout 0, or with the dropouts' keep masks given (the reference's module
+    tree: state_dict keys match), forward / losses as written in sasrec.py:107-158 on torch CPU. loss 'SSM' is
     the build's sampled softmax: CE over logits [pos | negs] with target 0."""
 
     def __init__(self, n_items, L, d, n_layers, n_heads, inner, eps):
@@ -668,20 +675,31 @@ class SASRecCPU(torch.nn.Module):
                                                       for _ in range(n_layers)])
         self.LayerNorm = torch.nn.LayerNorm(d, eps=eps)
 
-    def forward(self, item_seq, item_len):
+    def forward(self, item_seq, item_len, keeps=None, p_hidden=0.0, p_attn=0.0):
+        """keeps: None (dropout 0), or the boolean keep masks of a training forward, applied
+        where the reference applies dropout (sasrec.py:107-114, layers.py:338-461), each
+        scaled by 1 / (1 - p): 'emb' [B, L, d] after the embedding LayerNorm (p_hidden), and
+        per layer l 'attn{l}' [B, H, L, L] on the softmax probabilities (p_attn), 'out{l}'
+        [B, L, d] on dense(ctx) and 'ffn{l}' [B, L, d] on dense_2(h) before their residual
+        LayerNorms (p_hidden)."""
+        keeps = keeps or {}
         pos = torch.arange(item_seq.size(1)).unsqueeze(0).expand_as(item_seq)
         x = self.LayerNorm(self.item_embedding(item_seq) + self.position_embedding(pos))
+        x = _drop(x, keeps.get('emb'), p_hidden)
         am = (item_seq > 0).long().unsqueeze(1).unsqueeze(2)
         n = item_seq.size(1)
         sub = (torch.triu(torch.ones((1, n, n)), diagonal=1) == 0).unsqueeze(1).long()
         mask = (1.0 - (am * sub).float()) * -10000.0
-        for layer in self.trm_encoder.layer:
-            x = layer.feed_forward(layer.multi_head_attention(x, mask))
+        for l, layer in enumerate(self.trm_encoder.layer):
+            x = layer.multi_head_attention(x, mask, keeps.get(f'attn{l}'), p_attn,
+                                           keeps.get(f'out{l}'), p_hidden)
+            x = layer.feed_forward(x, keeps.get(f'ffn{l}'), p_hidden)
         idx = (item_len - 1).view(-1, 1, 1).expand(-1, -1, x.shape[-1])
         return x.gather(dim=1, index=idx).squeeze(1)
 
-    def calculate_loss(self, item_seq, item_len, pos, neg=None, loss_type='CE'):
-        s = self.forward(item_seq, item_len)
+    def calculate_loss(self, item_seq, item_len, pos, neg=None, loss_type='CE', keeps=None,
+                       p_hidden=0.0, p_attn=0.0):
+        s = self.forward(item_seq, item_len, keeps, p_hidden, p_attn)
         W = self.item_embedding.weight
         if loss_type == 'BPR':
             ps = torch.sum(s * self.item_embedding(pos), dim=-1)

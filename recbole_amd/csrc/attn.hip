@@ -16,8 +16,10 @@
 //             through the dropout), then all waves take 16-row strips of
 //             dQ = dS K / sqrt(dh), dK = dS^T Q / sqrt(dh), dV = P'^T dO.
 //
-// Dropout draws are counter-based: key = splitmix64(seed + c), c the forward's counter
-// value; for a row i = 16w + 4lk + r with r even and a column j, one draw
+// Dropout draws are counter-based: key = splitmix64(splitmix64(seed) ^ c), c the forward's
+// counter value (the seed and the counter enter separately: under seed + c a module at step
+// t + 1 drew the mask of the module with the next seed at step t; numpy restatement in
+// tests/drop_spec.py); for a row i = 16w + 4lk + r with r even and a column j, one draw
 // x = splitmix64(key ^ (((b H + h) 64 + i) 64 + j)) decides element (i, j) by its low 32
 // bits and element (i + 1, j) by its high 32 bits (kept iff < thr);
 // the keep bits are saved as the forward's ballot words (64 per (b, h): wave w, column
@@ -206,7 +208,7 @@ __global__ __launch_bounds__(kAtThreads) void attn_fwd_kernel(AttnArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 15, lk = lane >> 4;
   const int64_t base = b * L * ld + h * kAtD;
   const bool drop = a.keep != nullptr;
-  const uint64_t key = drop ? at_mix(a.seed + (uint64_t)a.counter[0]) : 0ull;
+  const uint64_t key = drop ? at_mix(at_mix(a.seed) ^ (uint64_t)a.counter[0]) : 0ull;
   {
     float4 kv[2][kAtPer];
     const float* const srcs[2] = {a.k + base, a.v + base};

@@ -49,6 +49,12 @@ __device__ __forceinline__ uint64_t ln_mix(uint64_t z) {
   return z ^ (z >> 31);
 }
 
+// the key of one draw: the seed and the counter enter separately (seed + c would give
+// site s at step t + 1 the key of site s + 1 at step t: sites' seeds differ by small words)
+__device__ __forceinline__ uint64_t ln_key(uint64_t seed, int64_t c) {
+  return ln_mix(ln_mix(seed) ^ (uint64_t)c);
+}
+
 // keep flags of the four elements e0 .. e0 + 3 (e0 a multiple of 4)
 __device__ __forceinline__ void ln_keep4(uint64_t key, uint64_t e0, uint32_t thr, bool (&k)[4]) {
   const uint64_t h0 = ln_mix(key ^ (e0 >> 1)), h1 = ln_mix(key ^ ((e0 >> 1) + 1));
@@ -75,7 +81,7 @@ __global__ __launch_bounds__(256) void seq_embed_ln_fwd_kernel(
   uint64_t key = 0;
   if (DROP) {
     const int64_t cv = dr.counter[0];
-    key = ln_mix(dr.seed + (uint64_t)cv);
+    key = ln_key(dr.seed, cv);
     if (blockIdx.x == 0 && threadIdx.x == 0) dr.drawn[0] = cv;
   }
   if (r >= n_rows) return;
@@ -123,7 +129,7 @@ __global__ __launch_bounds__(256) void seq_embed_ln_bwd_kernel(
     float* __restrict__ part_gamma, float* __restrict__ part_beta, LnDrop dr) {
   constexpr int LPR = D / 4, GPW = 64 / LPR;
   const int64_t cv = DROP ? dr.drawn[0] : 0;
-  const uint64_t key = DROP ? ln_mix(dr.seed + (uint64_t)cv) : 0ull;
+  const uint64_t key = DROP ? ln_key(dr.seed, cv) : 0ull;
   if (DROP && blockIdx.x == 0 && threadIdx.x == 0) dr.counter[0] = cv + 1;   // the next draw
   __shared__ float4 red_g[4 * GPW][LPR];
   __shared__ float4 red_b[4 * GPW][LPR];
@@ -199,8 +205,9 @@ __global__ __launch_bounds__(256) void seq_embed_ln_bwd_kernel(
 //   y = LayerNorm(drop(a) + b) in one pass (the sum is never written), and its backward
 //   from the saved mean / rstd with x = drop(a) + b recomputed; same arithmetic as K9a.
 //   DROP: the hidden dropout folded in (torch ran it as its own kernel each way). Draws are
-//   counter-based: key = splitmix64(seed + c), c the device counter's value at the forward
-//   (saved in drawn[0]); the backward redraws from drawn[0] and sets the counter to c + 1
+//   counter-based: key = splitmix64(splitmix64(seed) ^ c) (ln_key; numpy restatement in
+//   tests/drop_spec.py), c the device counter's value at the forward (saved in drawn[0]);
+//   the backward redraws from drawn[0] and sets the counter to c + 1
 //   (one store: a last-block ticket over the forward's 12,800 workgroups serialised that
 //   many atomics on one word, 153 us against 28 for the kernel itself);
 //   element e = row * D + column is kept iff the 32-bit half e & 1 of
@@ -219,7 +226,7 @@ __global__ __launch_bounds__(256) void add_ln_fwd_kernel(
   uint64_t key = 0;
   if (DROP) {
     const int64_t c = dr.counter[0];
-    key = ln_mix(dr.seed + (uint64_t)c);
+    key = ln_key(dr.seed, c);
     if (blockIdx.x == 0 && threadIdx.x == 0) dr.drawn[0] = c;
   }
   if (r < n_rows) {
@@ -271,7 +278,7 @@ __global__ __launch_bounds__(256) void add_ln_bwd_kernel(
   const int g = lane / LPR, l = lane % LPR;
   const float4 gm = reinterpret_cast<const float4*>(gamma)[l];
   const int64_t c = DROP ? dr.drawn[0] : 0;
-  const uint64_t key = DROP ? ln_mix(dr.seed + (uint64_t)c) : 0ull;
+  const uint64_t key = DROP ? ln_key(dr.seed, c) : 0ull;
   if (DROP && blockIdx.x == 0 && threadIdx.x == 0) dr.counter[0] = c + 1;   // the next draw
   float4 ag = make_float4(0.f, 0.f, 0.f, 0.f), ab = ag;
   const int64_t base = (int64_t)blockIdx.x * kLnRowsPerBlock;

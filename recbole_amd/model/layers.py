@@ -425,23 +425,53 @@ class _AddLNDropFn(torch.autograd.Function):
         return dxa, dxb, dgamma, dbeta, None, None, None
 
 
+# Site words of the folded dropouts (K9a / K9d: LN sites, K9e: attention sites). A site's
+# seed is site_seed(initial seed, word); its draws are keyed by
+# splitmix64(splitmix64(seed) ^ counter) in the kernels (csrc/seq.hip, csrc/attn.hip; numpy
+# restatement in tests/drop_spec.py). A model gives its modules words by their position when
+# it is assembled (assign_drop_sites, SASRec.__init__), so two models built after the same
+# init_seed draw the same masks; a module used on its own takes the next word of a process
+# counter from a range no model uses.
+LN_SITE, K9E_SITE = 0x1000, 0x2000            # + position in the model (< 0x1000)
+LN_SITE_LOOSE, K9E_SITE_LOOSE = 0x10000000, 0x20000000
 _DROP_SITES = [0]
+_ATTN_MODULES = [0]
+
+
+def site_seed(dev, word):
+    """The 64-bit seed of the dropout site `word`: from the device generator's initial seed
+    (torch.manual_seed sets it; no CPU generator draw, so the reference's CPU random
+    streams are untouched). Distinct words give distinct seeds."""
+    return (torch.cuda.default_generators[dev.index or 0].initial_seed() * 0x85EBCA6B
+            + word) & ((1 << 64) - 1)
 
 
 def _drop_rng(owner, dev):
-    """(seed, device draw counter, ticket) of a module's folded dropout: the seed from the
-    device generator's initial seed (no CPU generator draw) and the module's index."""
+    """(seed, device draw counter, ticket) of a module's folded dropout (an LN site)."""
     st = getattr(owner, '_ln_drop_rng', None)
     if st is None or st[1].device != dev:
-        if not hasattr(owner, '_ln_drop_index'):
-            owner._ln_drop_index = _DROP_SITES[0]
+        if getattr(owner, '_ln_drop_site', None) is None:
+            owner._ln_drop_site = LN_SITE_LOOSE + _DROP_SITES[0]
             _DROP_SITES[0] += 1
-        seed = (torch.cuda.default_generators[dev.index or 0].initial_seed() * 0x85EBCA6B
-                + 0x1000 + owner._ln_drop_index) & ((1 << 64) - 1)
-        st = (seed, torch.zeros(1, dtype=torch.int64, device=dev),
+        st = (site_seed(dev, owner._ln_drop_site),
+              torch.zeros(1, dtype=torch.int64, device=dev),
               torch.zeros(1, dtype=torch.int32, device=dev))
         owner._ln_drop_rng = st
     return st
+
+
+def assign_drop_sites(layers, first_ln_site=1):
+    """Dropout site words of a stack of TransformerLayers by position: layer l's attention
+    dropout is K9e site l, its out_dropout LN site first_ln_site + 2 l and its feed-forward
+    dropout LN site first_ln_site + 2 l + 1 (LN site 0 is left to the embedding dropout of
+    the model around the stack)."""
+    if first_ln_site + 2 * len(layers) > 0x1000:
+        raise ValueError(f'{len(layers)} layers: more dropout sites than site words')
+    for l, lm in enumerate(layers):
+        mha = lm.multi_head_attention
+        mha._attn_site, mha._attn_rng = K9E_SITE + l, None
+        for k, drop in enumerate((mha.out_dropout, lm.feed_forward.dropout)):
+            drop._ln_drop_site, drop._ln_drop_rng = LN_SITE + first_ln_site + 2 * l + k, None
 
 
 K9D_DROP = True     # the hidden dropout before add_layer_norm folded into K9d
@@ -491,7 +521,6 @@ class _GeluFn(torch.autograd.Function):
 
 SDPA = True     # fallback for shapes K9e does not take: torch's fused scaled_dot_product_attention
 K9E = True      # MultiHeadAttention's core through K9e (csrc/attn.hip) where it applies
-_ATTN_MODULES = [0]
 
 
 class _AttnFn(torch.autograd.Function):
@@ -559,19 +588,18 @@ class MultiHeadAttention(nn.Module):
         self.dense = nn.Linear(hidden_size, hidden_size)
         self.LayerNorm = nn.LayerNorm(hidden_size, eps=layer_norm_eps)
         self.out_dropout = nn.Dropout(hidden_dropout_prob)
-        self._attn_index = _ATTN_MODULES[0]    # K9e dropout stream of this module
-        _ATTN_MODULES[0] += 1
-        self._attn_rng = None
+        self._attn_site = None     # K9e dropout site word: the model's (assign_drop_sites),
+        self._attn_rng = None      # or a loose one at first use
 
     def _k9e_rng(self, dev):
-        """(seed, device draw counter, ticket) of this module's K9e dropout: the seed
-        from the device generator's initial seed (torch.manual_seed sets it; no CPU
-        generator draw, so the reference's CPU random streams are untouched) and the
-        module's construction index."""
+        """(seed, device draw counter, ticket) of this module's K9e dropout (site_seed of
+        its site word)."""
         if self._attn_rng is None or self._attn_rng[1].device != dev:
-            seed = (torch.cuda.default_generators[dev.index or 0].initial_seed()
-                    * 0x9E3779B1 + self._attn_index) & ((1 << 64) - 1)
-            self._attn_rng = (seed, torch.zeros(1, dtype=torch.int64, device=dev),
+            if self._attn_site is None:
+                self._attn_site = K9E_SITE_LOOSE + _ATTN_MODULES[0]
+                _ATTN_MODULES[0] += 1
+            self._attn_rng = (site_seed(dev, self._attn_site),
+                              torch.zeros(1, dtype=torch.int64, device=dev),
                               torch.zeros(1, dtype=torch.int32, device=dev))
         return self._attn_rng
 
@@ -681,6 +709,7 @@ class TransformerEncoder(nn.Module):
         layer = TransformerLayer(n_heads, hidden_size, inner_size, hidden_dropout_prob,
                                  attn_dropout_prob, hidden_act, layer_norm_eps)
         self.layer = nn.ModuleList([copy.deepcopy(layer) for _ in range(n_layers)])
+        assign_drop_sites(self.layer)
 
     def forward(self, hidden_states, attention_mask, output_all_encoded_layers=True):
         out = []

@@ -22,7 +22,7 @@ import torch.nn as nn
 from recbole_amd import ops
 from recbole_amd._native import check, lib, ptr, stream_handle
 from recbole_amd.model.abstract_recommender import SequentialRecommender
-from recbole_amd.model.layers import TransformerEncoder, _drop_rng, colsums
+from recbole_amd.model.layers import LN_SITE, TransformerEncoder, _drop_rng, colsums
 from recbole_amd.model.loss import BPRLoss
 
 
@@ -180,7 +180,7 @@ class SASRec(SequentialRecommender):
 
     # the training step has no host synchronisation or host-side branching on device
     # values (K9a / K9b / K3 launches with host-known sizes, deferred catch-ups on the
-    # device step counter, dropout through torch's capture-aware generator): the
+    # device step counter, dropout draws keyed by device counters the kernels advance): the
     # trainer may capture it in a HIP graph (trainer/graph_step.py)
     graph_step_safe = True
 
@@ -205,6 +205,8 @@ class SASRec(SequentialRecommender):
             layer_norm_eps=self.layer_norm_eps)
         self.LayerNorm = nn.LayerNorm(self.hidden_size, eps=self.layer_norm_eps)
         self.dropout = nn.Dropout(self.hidden_dropout_prob)
+        # the embedding dropout is LN site 0 of the model (the encoder numbered its own from 1)
+        self.dropout._ln_drop_site = LN_SITE
         if self.loss_type == 'BPR':
             self.loss_fct = BPRLoss()
         elif self.loss_type == 'CE':

@@ -1,33 +1,21 @@
 """K9d with the hidden dropout folded in (csrc/seq.hip, mirec_add_ln_drop_fwd/bwd_f32):
 LayerNorm(dropout(a) + b) of the transformer blocks (reference layers.py:338-461) against a
 float64 torch restatement that applies the keep flags of the kernel's draw specification
-(restated in numpy below: key = splitmix64(seed + c), element e kept iff the 32-bit half
-e & 1 of splitmix64(key ^ (e >> 1)) is below 2^32 (1 - p)); forward, dA, dB, dgamma, dbeta
-(fp32, 1e-4 relative), the drawn word and the backward's advance of the device counter."""
+(restated in numpy in tests/drop_spec.py: key = splitmix64(splitmix64(seed) ^ c), element e
+kept iff the 32-bit half e & 1 of splitmix64(key ^ (e >> 1)) is below 2^32 (1 - p));
+forward, dA, dB, dgamma, dbeta (fp32, 1e-4 relative), the drawn word and the backward's
+advance of the device counter; and the independence of the streams of a model's sites
+across steps (LN sites here, K9e's through mirec_attn_fwd_f32)."""
+import itertools
+
 import numpy as np
 import pytest
 import torch
 
+from tests import drop_spec
+from tests.drop_spec import ln_keep
+
 pytestmark = pytest.mark.gpu
-
-M64 = np.uint64(0xFFFFFFFFFFFFFFFF)
-
-
-def _mix(z):
-    with np.errstate(over='ignore'):
-        z = (z + np.uint64(0x9E3779B97F4A7C15)) & M64
-        z = ((z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)) & M64
-        z = ((z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)) & M64
-        return z ^ (z >> np.uint64(31))
-
-
-def _keep(seed, c, n_elems, p):
-    key = _mix(np.uint64((seed + c) & 0xFFFFFFFFFFFFFFFF))
-    e = np.arange(n_elems, dtype=np.uint64)
-    h = _mix(key ^ (e >> np.uint64(1)))
-    half = np.where((e & np.uint64(1)) == 1, h >> np.uint64(32), h & np.uint64(0xFFFFFFFF))
-    thr = min(4294967295, int(np.ldexp(1.0 - p, 32)))
-    return half < np.uint64(thr)
 
 
 @pytest.mark.parametrize('d', [64, 128])
@@ -58,7 +46,7 @@ def test_add_ln_drop_matches_restatement(dev, d, p):
                                       ptr(dxb), ptr(pg), ptr(pb), st), 'bwd')
     torch.cuda.synchronize(dev)
     assert int(counter.item()) == 42 and int(drawn.item()) == 41   # the backward advanced it
-    keep = torch.as_tensor(_keep(seed, 41, n * d, p).reshape(n, d))
+    keep = torch.as_tensor(ln_keep(seed, 41, n * d, p).reshape(n, d))
     assert abs(keep.float().mean().item() - (1 - p)) < 0.01
     A, B = a.double().requires_grad_(), b.double().requires_grad_()
     G, Bt = gamma.double().requires_grad_(), beta.double().requires_grad_()
@@ -122,7 +110,7 @@ def test_seq_embed_ln_drop_matches_restatement(dev, p):
     y.backward(gy.to(dev))
     torch.cuda.synchronize(dev)
     assert int(rng[1].item()) == 8
-    keep = torch.as_tensor(_keep(seed, 7, B * L * d, p).reshape(B, L, d))
+    keep = torch.as_tensor(ln_keep(seed, 7, B * L * d, p).reshape(B, L, d))
     assert abs(keep.float().mean().item() - (1 - p)) < 0.01
     E64, P64, G64, B64 = (t.double().requires_grad_() for t in (E, P, gamma, beta))
     x = E64[seq] + P64[None]
@@ -134,3 +122,73 @@ def test_seq_embed_ln_drop_matches_restatement(dev, p):
     torch.testing.assert_close(Pd.grad.cpu(), P64.grad.float(), rtol=1e-4, atol=2e-3)
     torch.testing.assert_close(Gd.grad.cpu(), G64.grad.float(), rtol=1e-4, atol=2e-3)
     torch.testing.assert_close(Bd.grad.cpu(), B64.grad.float(), rtol=1e-4, atol=2e-3)
+
+
+# ------------------------------------------------------------------ stream independence
+INITIAL_SEED = 2020
+
+
+def _assert_independent(masks, p, what):
+    """Every pair of masks agrees on a fraction within 0.03 of p^2 + (1 - p)^2 (two
+    independent Bernoulli(1 - p) fields; 0.03 is ~8 sigma at the 15,000+ elements used; the
+    numpy restatement alone stays within 0.0115)."""
+    want = p * p + (1 - p) ** 2
+    for (ka, a), (kb, b) in itertools.combinations(masks.items(), 2):
+        agree = float((a == b).mean())
+        assert abs(agree - want) <= 0.03, (what, ka, kb, agree)
+
+
+def test_ln_site_streams_independent(dev):
+    """The five LN sites of a 2-layer model (seeds from drop_spec's seed rule) x counters
+    0..3 through mirec_add_ln_drop_fwd_f32 with a = 1, b = 0 (the keep pattern is the sign
+    of the normalised output): 20 distinct keys, every mask equal to the specification,
+    every pair of masks independent. Under the earlier key rule splitmix64(seed + c), site
+    s at counter c + 1 drew the very mask of site s + 1 at counter c (agreement 1.0)."""
+    from recbole_amd._native import check, lib, ptr
+    n, d, p, eps = 257, 64, 0.5, 1e-5
+    a, b = torch.ones(n, d, device=dev), torch.zeros(n, d, device=dev)
+    gamma, beta = torch.ones(d, device=dev), torch.zeros(d, device=dev)
+    mean, rstd = torch.empty(n, device=dev), torch.empty(n, device=dev)
+    drawn = torch.empty(1, dtype=torch.int64, device=dev)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    seeds = [drop_spec.ln_site_seed(INITIAL_SEED, s) for s in
+             (drop_spec.LN_EMBEDDING, drop_spec.ln_attn_out(0), drop_spec.ln_ffn(0),
+              drop_spec.ln_attn_out(1), drop_spec.ln_ffn(1))]
+    assert len(set(seeds)) == 5
+    pairs = [(s, c) for s in seeds for c in range(4)]
+    assert len({int(drop_spec.key(s, c)) for s, c in pairs}) == 20
+    masks = {}
+    for seed, c in pairs:
+        counter = torch.full((1,), c, dtype=torch.int64, device=dev)
+        out = torch.empty_like(a)
+        check(lib().mirec_add_ln_drop_fwd_f32(ptr(a), ptr(b), n, d, ptr(gamma), ptr(beta), eps,
+                                              p, seed, ptr(counter), ptr(drawn), ptr(out),
+                                              ptr(mean), ptr(rstd), st), 'fwd')
+        got = (out > 0).cpu().numpy().reshape(-1)
+        assert int(drawn.item()) == c
+        assert np.array_equal(got, ln_keep(seed, c, n * d, p)), (hex(seed), c)
+        masks[(seed, c)] = got
+    _assert_independent(masks, p, 'LN sites')
+
+
+def test_k9e_site_streams_independent(dev):
+    """Two layers' K9e attention dropouts x counters 0..2 at (B, H, L) = (3, 2, 50): six
+    distinct keys, the saved keep bits equal to the specification, every pair of masks
+    independent."""
+    from tests.test_gpu_attention import _keep_from_words, _mask, _run
+    B, H, L, p = 3, 2, 50, 0.5
+    g = torch.Generator().manual_seed(11)
+    q, k, v = (torch.randn(B, L, H * 64, generator=g) for _ in range(3))
+    mask = _mask(B, L, g, 'sasrec')
+    seeds = [drop_spec.attn_site_seed(INITIAL_SEED, l) for l in range(2)]
+    ln_seeds = [drop_spec.ln_site_seed(INITIAL_SEED, s) for s in range(5)]
+    assert len(set(seeds + ln_seeds)) == 7              # K9e sites against LN sites too
+    pairs = [(s, c) for s in seeds for c in range(3)]
+    assert len({int(drop_spec.key(s, c)) for s, c in pairs}) == 6
+    masks = {}
+    for seed, c in pairs:
+        rng = (seed, torch.full((1,), c, dtype=torch.int64, device=dev), None)
+        got = _keep_from_words(_run(dev, q, k, v, mask, H, p, rng)['keep'], B, H, L).numpy()
+        assert np.array_equal(got, drop_spec.attn_keep(seed, c, B, H, L, p)), (hex(seed), c)
+        masks[(seed, c)] = got
+    _assert_independent(masks, p, 'K9e sites')

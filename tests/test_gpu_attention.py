@@ -4,7 +4,8 @@ recbole/model/layers.py:338-407) against a float64 torch restatement of the same
 all three input gradients: fp32 tolerance 1e-4 relative / 2e-5 absolute. With dropout the
 restatement applies the keep bits the kernel saved (their layout: csrc/attn.hip header),
 and the draws are checked for rate, freshness per forward (device counter) and
-reproducibility."""
+reproducibility; the saved bits themselves are checked against the numpy restatement of the
+draw rule (tests/drop_spec.py)."""
 import numpy as np
 import pytest
 import torch
@@ -121,6 +122,38 @@ def test_k9e_dropout(dev):
     rng[1].fill_(0)
     same = _run(dev, q, k, v, mask, H, p, rng)
     assert torch.equal(same['keep'], got['keep']) and torch.equal(same['out'], got['out'])
+
+
+@pytest.mark.parametrize('B,H,L,p', [(3, 2, 50, 0.3), (2, 1, 64, 0.5), (5, 2, 17, 0.1),
+                                     (4, 3, 33, 0.5), (6, 2, 1, 0.5)])
+def test_k9e_mask_matches_spec(dev, B, H, L, p):
+    """The keep bits K9e saved equal the draw rule of its header, restated in
+    tests/drop_spec.py (key from seed and counter, one draw per row pair and column, its
+    halves, bh = b H + h, the threshold), bit for bit: odd L (the last row's pair partner is
+    past the end), the tile edges L = 1 and 64, H = 3, a nonzero counter and a seed above
+    2^33. Forward and gradients against float64 with the specification's mask."""
+    from tests.drop_spec import attn_keep
+    seed, c = (1 << 33) + 987654321, 5
+    g = torch.Generator().manual_seed(B * 1000 + L)
+    q, k, v = (torch.randn(B, L, H * 64, generator=g) for _ in range(3))
+    mask = _mask(B, L, g, 'sasrec' if L in (50, 1) else 'random')
+    go = torch.randn(B, L, H * 64, generator=g)
+    rng = (seed, torch.full((1,), c, dtype=torch.int64, device=dev), None)
+    got = _run(dev, q, k, v, mask, H, p, rng, go)
+    assert int(rng[1].item()) == c + 1
+    want_keep = torch.as_tensor(attn_keep(seed, c, B, H, L, p))
+    keep = _keep_from_words(got['keep'], B, H, L)
+    assert torch.equal(keep, want_keep), int((keep != want_keep).sum())
+    if want_keep.numel() >= 15000:
+        rate = keep.float().mean().item()
+        assert abs(rate - (1 - p)) < 0.02, rate
+    qq, kk, vv = (x.double().requires_grad_() for x in (q, k, v))
+    want = _ref(qq, kk, vv, mask.double(), H, want_keep.double(), p)
+    want.backward(go.double())
+    _check(got['out'], want.detach(), 'out')
+    _check(got['dq'], qq.grad, 'dq')
+    _check(got['dk'], kk.grad, 'dk')
+    _check(got['dv'], vv.grad, 'dv')
 
 
 def test_multihead_attention_module_k9e(dev):

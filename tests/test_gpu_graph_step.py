@@ -10,7 +10,8 @@ import torch
 pytestmark = pytest.mark.gpu
 
 
-def _run(tmp_path, graphed, steps, window, model_name='DeepFM', **kw):
+def _run(tmp_path, graphed, steps, window, model_name='DeepFM', hidden_dropout_prob=0.0,
+         attn_dropout_prob=0.0, **kw):
     from recbole_amd.trainer import Trainer
     from recbole_amd.trainer.graph_step import GraphedTrainStep
     if model_name == 'DeepFM':
@@ -20,8 +21,8 @@ def _run(tmp_path, graphed, steps, window, model_name='DeepFM', **kw):
     else:
         from tests.test_gpu_sasrec import _pipeline
         config, train, valid, test, model = _pipeline(
-            tmp_path, adam_mode='deferred', train_batch_size=96, hidden_dropout_prob=0.0,
-            attn_dropout_prob=0.0, **kw)
+            tmp_path, adam_mode='deferred', train_batch_size=96,
+            hidden_dropout_prob=hidden_dropout_prob, attn_dropout_prob=attn_dropout_prob, **kw)
     tr = Trainer(config, model)
     opt = tr.optimizer
     assert getattr(opt, '_deferred', {}) or kw.get('loss_type') == 'CE'
@@ -81,6 +82,31 @@ def test_graphed_sasrec_step_bitwise(tmp_path, loss):
         assert torch.equal(sa[k], sb[k]), k
     for (x1, y1), (x2, y2) in zip(ma, mb):
         assert torch.equal(x1, x2) and torch.equal(y1, y2)
+
+
+@pytest.mark.parametrize('loss', ['SSM', 'BPR'])
+def test_graphed_sasrec_step_with_dropout_bitwise(tmp_path, loss):
+    """The same with both dropout probabilities 0.3 at hidden size 128, two heads (head size
+    64: K9e, K9a and K9d draw from their device counters): the captured step equals the eager
+    step bit for bit, and every replay draws new masks — no two consecutive losses on the
+    same batch are equal."""
+    kw = {'loss_type': loss, 'training_neg_sample_num': 4 if loss == 'SSM' else 1,
+          'hidden_size': 128, 'n_heads': 2}
+    steps, window = 24, 8
+    la, sa, ma, ng, na = _run(tmp_path / 'g', True, steps, window, 'SASRec',
+                              hidden_dropout_prob=0.3, attn_dropout_prob=0.3, **kw)
+    lb, sb, mb, _, nb = _run(tmp_path / 'e', False, steps, window, 'SASRec',
+                             hidden_dropout_prob=0.3, attn_dropout_prob=0.3, **kw)
+    assert na == nb == steps
+    assert ng >= steps // 2
+    assert la == lb
+    for k in sa:
+        assert torch.equal(sa[k], sb[k]), k
+    for (x1, y1), (x2, y2) in zip(ma, mb):
+        assert torch.equal(x1, x2) and torch.equal(y1, y2)
+    n_batches = 6                                         # _run cycles over six batches
+    for k in range(n_batches, steps):
+        assert la[k] != la[k - n_batches], (k, la[k])
 
 
 def test_copy_many(dev):
