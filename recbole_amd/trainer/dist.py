@@ -39,18 +39,34 @@ def active_group(config=None):
     return tdist.group.WORLD
 
 
+def all_gather_blocks(out, mine, group):
+    """Every rank's block -> out [G, ...] in rank order (one collective). `mine` may
+    be out[rank] itself (in place). RCCL: one call; gloo (CPU-staged; tests): list form."""
+    if str(tdist.get_backend(group)) == 'nccl':
+        tdist.all_gather_into_tensor(out, mine, group=group)
+    else:
+        if mine.untyped_storage().data_ptr() == out.untyped_storage().data_ptr():
+            mine = mine.clone()
+        tdist.all_gather(list(out.unbind(0)), mine, group=group)
+
+
 def _gather_cat(t, group):
     """all-gather of equal-shaped tensors, concatenated along dim 0 in rank order."""
-    G = tdist.get_world_size(group)
     t = t.contiguous()
+    G = tdist.get_world_size(group)
+    out = torch.empty((G,) + tuple(t.shape), dtype=t.dtype, device=t.device)
+    all_gather_blocks(out, t, group)
+    return out.view((G * t.shape[0],) + tuple(t.shape[1:]))
+
+
+def all_to_all_blocks(recv, send, group):
+    """All-to-all of equal blocks along dim 0 (block g of `send` to rank g)."""
     if str(tdist.get_backend(group)) == 'nccl':
-        out = torch.empty((G * t.shape[0],) + tuple(t.shape[1:]), dtype=t.dtype,
-                          device=t.device)
-        tdist.all_gather_into_tensor(out, t, group=group)
-        return out
-    parts = [torch.empty_like(t) for _ in range(G)]
-    tdist.all_gather(parts, t, group=group)
-    return torch.cat(parts)
+        tdist.all_to_all_single(recv, send, group=group)
+    else:
+        r = torch.empty(recv.shape, dtype=recv.dtype)
+        tdist.all_to_all_single(r, send.cpu(), group=group)
+        recv.copy_(r)
 
 
 def all_to_all_v(send, send_counts, group):

@@ -1,4 +1,4 @@
-"""Fused train step and full-sort evaluation for embedding models (BPR-MF).
+"""Fused train step for embedding models (BPR-MF).
 
 One training step of Trainer._train_epoch (trainer.py:157-174) for a pairwise
 model with learner 'adam', as hand-written gfx950 kernels with no host
@@ -36,19 +36,24 @@ row is next touched (or at the per-chunk flush), with the same per-element
 arithmetic, so the parameters after a flush are bit-identical to the streamed
 schedule's while a step moves only the rows its batch touches. Parameters are
 complete after end_epoch() / sync_params().
+
+The chunk plan (sizes, ramp, entry / flush flags) is trainer/chunk_plan.py; the
+row-sharded step is trainer/sharded.py and the evaluations are trainer/fused_eval.py
+(both re-exported here).
 """
 from __future__ import annotations
 
 import ctypes
-import logging
 import math
 import os
+from types import SimpleNamespace
 
 import numpy as np
 import torch
 
 from recbole_amd import ops
-from recbole_amd._native import AdamTable, check, lib
+from recbole_amd._native import AdamTable, ChunkPrep, check, lib
+from recbole_amd.trainer import chunk_plan
 from recbole_amd.trainer.exchange import ExchangeLayout
 
 # K35 record widths (int32 per touched-row slot / per grouped position, include/mirec.h
@@ -107,35 +112,39 @@ def _prep_streams_for(dev, n=2):
     return chosen
 
 
+class _Lists(object):
+    """One table's grouping of a chunk's batches, each an int32 device array with one
+    block per batch: `perm` the key slots ordered by table row, `uniq` the distinct rows,
+    `seg` each row's bounds in perm, `nu` the number of distinct rows; deferred Adam
+    also `ahead` / `nah`: the rows batch c+1 reads and batch c does not touch."""
+
+    def __init__(self, C, per, dev, ahead):
+        """For C batches of `per` key slots."""
+        i32 = dict(dtype=torch.int32, device=dev)
+        self.perm, self.uniq = torch.empty(C * per, **i32), torch.empty(C * per, **i32)
+        self.seg, self.nu = torch.empty(C * (per + 1), **i32), torch.zeros(C, **i32)
+        self.ahead = torch.empty(C * per, **i32) if ahead else None
+        self.nah = torch.zeros(C, **i32) if ahead else None
+
+
 class _Slot(object):
     """Buffers of one chunk of prepared batches (global-batch keys and groupings;
     for G > 1 also this rank's local key slices)."""
 
-    def __init__(self, C, B, T, G, dev, ahead):
+    def __init__(self, C, B, T, G, dev, ahead, tab=None):
         Bg = G * B
         KI = (1 + T) * Bg
         self.user_keys = torch.empty(C * Bg, dtype=torch.int64, device=dev)
         self.item_keys = torch.empty(C * KI, dtype=torch.int64, device=dev)
+        self.lu = self.li = None
         if G > 1:
             self.lu = torch.empty(C * B, dtype=torch.int64, device=dev)
             self.li = torch.empty(C * (1 + T) * B, dtype=torch.int64, device=dev)
-        self.u_perm = torch.empty(C * Bg, dtype=torch.int32, device=dev)
-        self.u_uniq = torch.empty(C * Bg, dtype=torch.int32, device=dev)
-        self.u_seg = torch.empty(C * (Bg + 1), dtype=torch.int32, device=dev)
-        self.u_nu = torch.zeros(C, dtype=torch.int32, device=dev)
-        self.i_perm = torch.empty(C * KI, dtype=torch.int32, device=dev)
-        self.i_uniq = torch.empty(C * KI, dtype=torch.int32, device=dev)
-        self.i_seg = torch.empty(C * (KI + 1), dtype=torch.int32, device=dev)
-        self.i_nu = torch.zeros(C, dtype=torch.int32, device=dev)
-        if ahead:                    # deferred Adam: rows batch c+1 reads, batch c does not touch
-            self.u_ahead = torch.empty(C * Bg, dtype=torch.int32, device=dev)
-            self.u_nah = torch.zeros(C, dtype=torch.int32, device=dev)
-            self.i_ahead = torch.empty(C * KI, dtype=torch.int32, device=dev)
-            self.i_nah = torch.zeros(C, dtype=torch.int32, device=dev)
+        # per table (users, items): the grouping of each batch's keys
+        self.tab = tab or [_Lists(C, per, dev, ahead) for per in (Bg, KI)]
         self.records = None          # K35 row / contribution records (FusedBPRTrainStep)
-        self.ready = torch.cuda.Event()
-        self.walked = torch.cuda.Event()
-        self.free = torch.cuda.Event()
+        self.prep = None             # mirec_chunk_prep descriptor (_chunk_prep)
+        self.ready, self.walked, self.free = (torch.cuda.Event() for _ in range(3))
         # torch creates an event's HIP object at its first record (hipEventCreate, tens of
         # microseconds of host time): record each one now, so a timed region never pays it
         cur = torch.cuda.current_stream(dev)
@@ -143,6 +152,7 @@ class _Slot(object):
             ev.record(cur)
         self.free_recorded = False
         self.group_pending = False   # walked, grouping not yet issued
+        self.ready_on_model = False  # prepared on the model's stream: no wait for `ready`
         self.chunk = None            # (first global batch, n batches, global batch size)
         self.graphs = {}             # (n batches, entry, flush) -> HIP graph of the model side
 
@@ -159,7 +169,20 @@ class FusedBPRTrainStep(object):
     sampler walk and the grouping of the global batch are computed on every rank
     (cheap, on the prep stream), so each rank's result is bit-identical to ONE GPU
     running the global batch (tables and Adam state are replicas: 288 GB per GPU).
-    A ragged last batch is computed whole on every rank (no exchange)."""
+    A ragged last batch is computed whole on every rank (no exchange).
+
+    Subclass contract (trainer/sharded.py; tests/test_fused_signatures.py binds every call
+    this class makes to the overrides). __init__ sets the shape, the streams and the
+    persistent scalars, then calls ONE overridable method, as its last statement:
+      _allocate()     the slots, the tables' buffers, _n_max; ends with _fill_tables()
+    A subclass sets what its _allocate needs before it calls this __init__. It may also
+    override, with these argument lists:
+      _fill_tables()  point self._tables at p / m / v / last (batch-independent)
+      _adam_state()   -> [(m, v, last)] per table
+      _prepare(slot, chunk, on=None), _step(slot, c, Bc, stream, step_off, ahead),
+      _finish(c0, n_steps, Bc, stream), _entry_lists(slot) -> [(rows, count)] per table,
+      _enter_chunk(k, stream), begin_epoch(cuts=(), hold_prep_from=None, flush_at=()),
+      end_epoch(n_done=None), close()"""
 
     CHUNK = 64
     SLOTS = 3                     # chunk buffers in flight (walk, grouping, model)
@@ -176,16 +199,20 @@ class FusedBPRTrainStep(object):
     # row is touched, and its slowest wave sets the step time: measured on C2 (64
     # warm-up + 256 steps) 18.0 M positives/s at 64, 12.4 M at 256, 12.3 M at 1,024.
     FLUSH_EVERY = 64
+    # a flush of a table whose rows are mostly current (zero state) runs R rows per wave
+    # (mirec_adam_flush_rows_f32) when about one row per R would lag
+    FLUSH_SPARSE_MAX_ROWS = 8
     # A chunk the model side waits for at once (pipeline (re)start: the epoch's first chunk,
     # or a timed region that holds its own preparation) is walked and grouped on the model's
     # stream — no hand-off between hardware queues (≈ 20 µs each) before the first step —
     # and the next chunks' walks are issued on the prep stream right behind its walk (they
     # run beside its grouping and steps). MIREC_MAIN_FIRST=0: the prep streams for it too.
     MAIN_FIRST = os.environ.get('MIREC_MAIN_FIRST', '1') != '0'
-    _last_walked = None           # event after the latest issued walk (begin_epoch resets)
-    _deferred_waits = ()          # cross-stream waits on a restart chunk, issued with the next walk
-    _urgent = False               # the next chunk prepared is the one after a restart
-    _late_top_up = None           # restart chunk whose next walks follow its model launch
+    # K4s (mirec_sample_walk_spec): the chunk's walk by speculation (exact; two launches
+    # per 16 batches instead of a serial walk of ~10 us per batch)
+    SPEC_WALK = os.environ.get('MIREC_SPEC_WALK', '1') != '0'
+    # (RAMP, FLUSH_EVERY, FLUSH_SPARSE_MAX_ROWS and MAIN_FIRST are read at begin_epoch /
+    # when a chunk is entered: an instance may set its own after construction)
 
     def __init__(self, model, optimizer, train_data, chunk=None, use_graph=True,
                  adam_mode='deferred', dist=None, fused_step=None):
@@ -207,23 +234,24 @@ class FusedBPRTrainStep(object):
         if dist is not None:
             import torch.distributed as tdist
             self.G, self.rank = tdist.get_world_size(dist), tdist.get_rank(dist)
-            self._backend = str(tdist.get_backend(dist))
-            if self._backend != 'nccl':        # host-staged collectives cannot be captured
-                self.use_graph = use_graph = False
+            if str(tdist.get_backend(dist)) != 'nccl':   # host-staged collectives cannot
+                self.use_graph = False                   # be captured
         else:
-            self.G, self.rank, self._backend = 1, 0, None
+            self.G, self.rank = 1, 0
         B, T, G, d = self.B, self.times, self.G, self.pU.shape[1]
         self.Bg = G * B                            # positives per optimizer step
         self.d = d
         dev = self.device
-        self.layout = ExchangeLayout(G, B, T, d)
-        # gradient rows of the (global) batch: [user rows | item rows]
-        self.xbuf = torch.empty(self.Bg * (2 + T) * d, dtype=torch.float32, device=dev)
-        # data parallel: per-rank [losses | coefficients] blocks, all-gathered per step
-        self.xchg = torch.empty(G * self.layout.W, dtype=torch.float32, device=dev)
-        self.loss_k = torch.empty(self.C * self.Bg, dtype=torch.float32, device=dev)
         deferred = adam_mode == 'deferred'
-        self.slots = [_Slot(self.C, B, T, G, dev, deferred) for _ in range(self.SLOTS)]
+        # K35 (csrc/step.hip): the model side of a step in ONE launch (BPR + the touched
+        # rows' Adam + look-ahead), bit-identical to K3 + K5. One GPU, deferred schedule;
+        # needs the parity buffers of p (state after t steps in t & 1 ? alt : p)
+        applies = deferred and G == 1 and d in (64, 128, 256)
+        if fused_step and not applies:
+            raise ValueError('fused_step needs adam_mode="deferred", one rank and d in '
+                             '{64, 128, 256}')
+        self.fused_step = applies if fused_step is None else bool(fused_step)
+        self.loss_k = torch.empty(self.C * self.Bg, dtype=torch.float32, device=dev)
         self.samp_ws = torch.empty(lib().mirec_sample_walk_workspace_size(self.Bg, T),
                                    dtype=torch.uint8, device=dev)
         self.sort_ws = None
@@ -238,27 +266,48 @@ class FusedBPRTrainStep(object):
         self.ticket = torch.zeros(1, dtype=torch.int32, device=dev)   # mirec_chunk_finish
         self.kernel_events = None   # list -> (name, start, end) HIP events (bench.py)
         self.kernel_uniq = []       # per eager step: [touched users, touched items]
-        self._plan, self._plan_starts = [], None
-        self._current = True        # no step enqueued since the last flush
         self.n_eager_steps = 0      # steps launched outside a captured chunk graph
+        self._rec_w = {}            # batch size -> K35 record widths (_rec_ints)
+        self._spec_buf = self._spec_stats = None    # speculative walk (_spec_ws)
+        self._gs_R = self._gs = None                # _grad_scale's last (rows, value)
+        # the epoch's state (begin_epoch)
+        self._users = self._items = None
+        self.n_batches = 0
+        self._plan, self._flags, self._flush_at = [], [], set()
+        self._busy0 = None          # rows outside the zero state at the epoch start
+        self._batches_enqueued = 0
+        self._current = True        # no step enqueued since the last flush
+        self._next_chunk = self._next_group = self._prep_limit = 0
+        self._cur = None            # chunk index being consumed
+        self._last_walked = None    # event after the latest issued walk
+        self._deferred_waits = []   # cross-stream waits on a restart chunk, issued with the next walk
+        self._urgent = False        # the next chunk prepared is the one after a restart
+        self._late_top_up = None    # restart chunk whose next walks follow its model launch
         self.opt._ensure_state(self.pU)
         self.opt._ensure_state(self.pI)
         self._tables = (AdamTable * 2)()
+        g = self.opt.param_groups[0]
+        self._adam_args = (g['betas'][0], g['betas'][1], g['eps'], g['weight_decay'])
+        self._allocate()
+
+    def _allocate(self):
+        """The allocation hook (the last statement of __init__): the slots, the tables'
+        buffers and _n_max (the most rows a step touches per table), then _fill_tables()."""
+        B, T, G, d, dev = self.B, self.times, self.G, self.d, self.device
+        deferred = self.adam_mode == 'deferred'
+        self.layout = ExchangeLayout(G, B, T, d)
+        # gradient rows of the (global) batch: [user rows | item rows]
+        self.xbuf = torch.empty(self.Bg * (2 + T) * d, dtype=torch.float32, device=dev)
+        # data parallel: per-rank [losses | coefficients] blocks, all-gathered per step
+        self.xchg = torch.empty(G * self.layout.W, dtype=torch.float32, device=dev)
+        self.slots = [_Slot(self.C, B, T, G, dev, deferred) for _ in range(self.SLOTS)]
+        self.lastU = self.lastI = None
         if deferred:
             self.lastU = torch.zeros(self.nU, dtype=torch.int32, device=dev)
             self.lastI = torch.zeros(self.nI, dtype=torch.int32, device=dev)
-        # K35 (csrc/step.hip): the model side of a step in ONE launch (BPR + the touched
-        # rows' Adam + look-ahead), bit-identical to K3 + K5. One GPU, deferred schedule;
-        # needs the parity buffers of p (state after t steps in t & 1 ? alt : p)
-        if fused_step is None:
-            fused_step = deferred and G == 1 and d in (64, 128, 256)
-        if fused_step and not (deferred and G == 1 and d in (64, 128, 256)):
-            raise ValueError('fused_step needs adam_mode="deferred", one rank and d in '
-                             '{64, 128, 256}')
-        self.fused_step = bool(fused_step)
         self.pU_alt = torch.empty_like(self.pU.data) if self.fused_step else None
         self.pI_alt = torch.empty_like(self.pI.data) if self.fused_step else None
-        self._rec_w = {}
+        self._step_scratch = None
         if self.fused_step:          # K35 records per slot (mirec_step_records, prep stream)
             for sl in self.slots:
                 sl.records = [torch.empty(self.C * w, dtype=torch.int32, device=dev)
@@ -266,82 +315,23 @@ class FusedBPRTrainStep(object):
             # split rows' hand-off scratch (one launch at a time on the compute stream)
             self._step_scratch = ops.step_scratch(self.Bg, T, d, dev)
         self._n_max = (ctypes.c_int64 * 2)(self.Bg, (1 + T) * self.Bg)
-        g = self.opt.param_groups[0]
-        self._adam_args = (g['betas'][0], g['betas'][1], g['eps'], g['weight_decay'])
         self._fill_tables()
 
     # ------------------------------------------------------------------ data side
-    def _chunks(self, cuts=(), ramps=(0,)):
-        """(first global batch, batches, global batch size) per chunk: chunks of at
-        most C full batches, starting at 0 and at every batch index in `cuts`, then
-        the ragged last batch on its own. From each batch index in `ramps` (where
-        the prep pipeline starts empty) up to the next cut, the chunk sizes ramp up
-        (RAMP, then C): the first steps wait for a 4-batch walk, not a C-batch one,
-        and each next walk runs beside the previous chunk's steps."""
-        n = self._users.numel()
-        full = n // self.Bg
-        bounds = sorted({0, full} | {int(c) for c in cuts if 0 < int(c) < full})
-        ramp_at = {int(r) for r in ramps}
-        out = []
-        for lo, hi in zip(bounds[:-1], bounds[1:]):
-            ri = 0 if lo in ramp_at else len(self.RAMP)
-            b0 = lo
-            while b0 < hi:
-                size = self.RAMP[ri] if ri < len(self.RAMP) else self.C
-                ri += 1
-                nb = min(size, self.C, hi - b0)
-                out.append((b0, nb, self.Bg))
-                b0 += nb
-        if n % self.Bg:
-            out.append((full, 1, n % self.Bg))
-        return out
-
-    def _chunk_flags(self, plan):
-        """(entry, flush) per chunk of the deferred schedule: a chunk flushes every
-        row at its end once FLUSH_EVERY or more steps have run since the last flush, or
-        when the next chunk would take the count past 1.5 x FLUSH_EVERY (the ramp's
-        4 + 8 + 16 + 32 steps flush before the first 64-step chunk instead of after it),
-        and before a ragged batch / the end; a chunk after one that did not flush starts
-        with an entry catch-up of the rows its first batch reads. `flush` is False or
-        the flush's rows per wave per table (_flush_rows: a tuple, part of the chunk
-        graph's key)."""
-        flags, since = [], 0
-        at = getattr(self, '_flush_at', set())
-        for i, (b0, nb, Bc) in enumerate(plan):
-            entry = since > 0
-            since += nb
-            nxt_full = i + 1 < len(plan) and plan[i + 1][2] == self.Bg
-            nxt_nb = plan[i + 1][1] if i + 1 < len(plan) else 0
-            flush = (since >= self.FLUSH_EVERY or since + nxt_nb > self.FLUSH_EVERY * 3 // 2
-                     or not nxt_full or b0 + nb in at)
-            if flush:
-                since = 0
-            flags.append((entry, self._flush_rows(b0 + nb) if flush else False))
-        return flags
-
-    # a flush of a table whose rows are mostly current (zero state) runs R rows per wave
-    # (mirec_adam_flush_rows_f32) when about one row per R would lag
-    FLUSH_SPARSE_MAX_ROWS = 8
-
     def _flush_rows(self, b_end):
-        """Rows per wave of the flush after global batch b_end - 1, per table: an upper
-        bound on the rows that can lag = the rows outside the zero state at the epoch
-        start + every row the steps since then touched (B users, (1+T)B item slots per
-        step); R = the largest power of two <= FLUSH_SPARSE_MAX_ROWS with R x that
-        fraction <= 1 (one wave per row, R = 1, where most rows lag)."""
-        if self.adam_mode != 'deferred' or self.d < 64:
-            return (1, 1)
-        out = []
-        for q, per in enumerate((self.Bg, (1 + self.times) * self.Bg)):
-            n_rows, busy0 = self._tables[q].n_rows, self._busy0[q]   # (a shard when sharded)
-            frac = min(1.0, (busy0 + b_end * per) / max(n_rows, 1))
-            r = 1
-            while r * 2 <= self.FLUSH_SPARSE_MAX_ROWS and r * 2 * frac <= 1.0:
-                r *= 2
-            out.append(r)
-        return tuple(out)
+        """Rows per wave per table of a flush after global batch b_end - 1
+        (chunk_plan.flush_rows; the tables' rows are a shard's when sharded)."""
+        return chunk_plan.flush_rows(b_end, self.Bg, self.times, self.adam_mode, self.d,
+                                     [t.n_rows for t in self._tables], self._busy0,
+                                     self.FLUSH_SPARSE_MAX_ROWS)
 
-    def _sharded(self, Bc):
+    def _chunk_of(self, b):
+        """Index of the plan chunk holding global batch b."""
+        return chunk_plan.chunk_of(self._plan, b)
+
+    def _dp_slice(self, Bc):
+        """A batch of Bc positives is a full global batch of which this rank runs its
+        slice of B (replicated data parallelism, G > 1); a ragged batch runs whole."""
         return self.G > 1 and Bc == self.Bg
 
     def _prepare(self, slot, chunk, on=None):
@@ -349,81 +339,88 @@ class FusedBPRTrainStep(object):
         pipeline (re)start whose chunk the model side waits for at once — the whole
         preparation on that stream (no cross-queue hand-off on the critical path; the
         prep and group streams order their next launches after it)."""
-        b0, nb, Bc = chunk
-        T = self.times
-        KI = (1 + T) * Bc
         if slot.free_recorded and on is None and not slot.free.query():
             self.prep_stream.wait_event(slot.free)     # (a completed event needs no wait)
-        if not self._sharded(Bc):
-            # keys, K4 walk, K2 groupings and look-ahead lists: one native call
-            # (mirec_prepare_chunk) on the prep stream
-            cp = self._chunk_prep(slot)
-            cp.users, cp.items = self._users.data_ptr(), self._items.data_ptr()
-            cp.s0, cp.n_batches, cp.Bc = b0 * self.Bg, nb, Bc
-            samp = self.data.sampler
-            if samp.alias is not None:              # fast mode: draw ids of this chunk
-                thr, idx, cp.alias_seed, cp.alias_counter = samp.alias_args(
-                    self.device, nb * Bc * T)
-                cp.alias_thr, cp.alias_idx, cp.n_alias = thr.data_ptr(), idx.data_ptr(), thr.numel()
-            st = on if on is not None else self.prep_stream
-            slot.ready_on_model = on is not None
-            if on is None:
-                self._apply_deferred_waits()
-            lw = self._last_walked
-            if on is not None and lw is not None and not lw.query():
-                # the walk pointer and the speculative walk's workspace are sequential
-                # state: a walk on the model's stream follows every walk issued before it
-                on.wait_event(lw)
-            check(lib().mirec_prepare_chunk_walk(ctypes.byref(cp), st.cuda_stream),
-                  'mirec_prepare_chunk_walk')
-            slot.walked.record(st)
-            self._last_walked = slot.walked
-            slot.chunk = chunk
-            if on is None:
-                if self._urgent:
-                    # the chunk right after a restart: its grouping at once, on the same
-                    # stream behind its walk (no hand-off between hardware queues)
-                    self._urgent = False
-                    check(lib().mirec_prepare_chunk_group(ctypes.byref(cp), st.cuda_stream),
-                          'mirec_prepare_chunk_group')
-                    slot.ready.record(st)
-                    self.group_stream.wait_event(slot.ready)     # shared sort workspace
-                    slot.group_pending = False
-                    return
-                slot.group_pending = True      # the grouping half: _issue_groups
-                return
-            check(lib().mirec_prepare_chunk_group(ctypes.byref(cp), st.cuda_stream),
-                  'mirec_prepare_chunk_group')
-            slot.ready.record(st)
+        if self._dp_slice(chunk[2]):
+            self._prepare_dp(slot, chunk)
+        else:
+            self._prepare_native(slot, chunk, on)
+
+    def _prepare_native(self, slot, chunk, on):
+        """keys, K4 walk, K2 groupings and look-ahead lists: two native calls
+        (mirec_prepare_chunk_walk / _group)."""
+        b0, nb, Bc = chunk
+        cp = self._chunk_prep(slot)
+        cp.users, cp.items = self._users.data_ptr(), self._items.data_ptr()
+        cp.s0, cp.n_batches, cp.Bc = b0 * self.Bg, nb, Bc
+        samp = self.data.sampler
+        if samp.alias is not None:              # fast mode: draw ids of this chunk
+            thr, idx, cp.alias_seed, cp.alias_counter = samp.alias_args(
+                self.device, nb * Bc * self.times)
+            cp.alias_thr, cp.alias_idx, cp.n_alias = thr.data_ptr(), idx.data_ptr(), thr.numel()
+        st = on if on is not None else self.prep_stream
+        slot.ready_on_model = on is not None
+        if on is None:
+            self._apply_deferred_waits()
+        lw = self._last_walked
+        if on is not None and lw is not None and not lw.query():
+            # the walk pointer and the speculative walk's workspace are sequential
+            # state: a walk on the model's stream follows every walk issued before it
+            on.wait_event(lw)
+        check(lib().mirec_prepare_chunk_walk(ctypes.byref(cp), st.cuda_stream),
+              'mirec_prepare_chunk_walk')
+        slot.walked.record(st)
+        self._last_walked = slot.walked
+        slot.chunk = chunk
+        if on is None and not self._urgent:
+            slot.group_pending = True      # the grouping half: _issue_groups
+            return
+        self._group_on(slot, st)
+        if on is None:
+            # the chunk right after a restart: its grouping at once, on the same
+            # stream behind its walk (no hand-off between hardware queues)
+            self._urgent = False
+            self.group_stream.wait_event(slot.ready)     # shared sort workspace
+        else:
             # the prep / group streams' waits on this chunk (the next walks continue its walk
             # pointer; the sort workspace is shared) go in with the next walk — after the
             # chunk's model launch, so the host's time first goes to what the GPU reaches first
             self._deferred_waits = [(self.prep_stream, slot.walked),
                                     (self.group_stream, slot.ready)]
-            slot.group_pending = False
-            return
+
+    def _copy_keys_and_walk(self, slot, chunk):
+        """On the current stream, with torch ops: the chunk's users and positive items
+        into the slot's key rows and the K4 walk of its negatives. Returns the chunk's
+        (user keys, item keys)."""
+        b0, nb, Bc = chunk
+        T = self.times
+        KI = (1 + T) * Bc
+        s0 = b0 * self.Bg
+        users = slot.user_keys[:nb * Bc]
+        users.copy_(self._users[s0:s0 + nb * Bc])
+        keys = slot.item_keys[:nb * KI].view(nb, 1 + T, Bc)
+        keys[:, 0, :].copy_(self._items[s0:s0 + nb * Bc].view(nb, Bc))
+        neg = slot.item_keys[Bc:nb * KI]                    # first batch's neg row
+        self.data.sampler.launch_batches(users, Bc, nb, T, neg, out_stride=KI, ws=self.samp_ws)
+        return users, slot.item_keys[:nb * KI]
+
+    def _prepare_dp(self, slot, chunk):
+        """A chunk of full global batches, G > 1: walk and groupings of the global
+        batches with torch-level ops on the prep stream, and this rank's key slices."""
+        _, nb, Bc = chunk
+        T = self.times
+        KI = (1 + T) * Bc
         with torch.cuda.stream(self.prep_stream):
-            s0 = b0 * self.Bg
-            users = slot.user_keys[:nb * Bc]
-            users.copy_(self._users[s0:s0 + nb * Bc])
-            keys = slot.item_keys[:nb * KI].view(nb, 1 + T, Bc)
-            keys[:, 0, :].copy_(self._items[s0:s0 + nb * Bc].view(nb, Bc))
-            neg = slot.item_keys[Bc:nb * KI]                    # first batch's neg row
-            self.data.sampler.launch_batches(users, Bc, nb, T, neg, out_stride=KI,
-                                             ws=self.samp_ws)
-            self.sort_ws = ops.segment_sort_batched(users, Bc, self.nU, slot.u_perm,
-                                                    slot.u_uniq, slot.u_seg, slot.u_nu,
-                                                    ws=self.sort_ws)
-            self.sort_ws = ops.segment_sort_batched(slot.item_keys[:nb * KI], KI, self.nI,
-                                                    slot.i_perm, slot.i_uniq, slot.i_seg,
-                                                    slot.i_nu, ws=self.sort_ws)
+            users, items = self._copy_keys_and_walk(slot, chunk)
+            for l, keys, per, n in zip(slot.tab, (users, items), (Bc, KI), (self.nU, self.nI)):
+                self.sort_ws = ops.segment_sort_batched(keys, per, n, l.perm, l.uniq, l.seg,
+                                                        l.nu, ws=self.sort_ws)
             lay, g, B = self.layout, self.rank, self.B
             slot.lu[:nb * B].view(nb, B).copy_(lay.local_users(users, g))
-            slot.li[:nb * (1 + T) * B].view(nb, 1 + T, B).copy_(
-                lay.local_items(slot.item_keys[:nb * KI], g))
+            slot.li[:nb * (1 + T) * B].view(nb, 1 + T, B).copy_(lay.local_items(items, g))
             if self.adam_mode == 'deferred':
-                ops.uniq_ahead_diff(slot.u_uniq, slot.u_nu, Bc, nb, slot.u_ahead, slot.u_nah)
-                ops.uniq_ahead_diff(slot.i_uniq, slot.i_nu, KI, nb, slot.i_ahead, slot.i_nah)
+                for l, per in zip(slot.tab, (Bc, KI)):
+                    ops.uniq_ahead_diff(l.uniq, l.nu, per, nb, l.ahead, l.nah)
             slot.ready.record(self.prep_stream)
         slot.chunk = chunk
 
@@ -437,18 +434,18 @@ class FusedBPRTrainStep(object):
         group stream, after the chunk's walk."""
         self._apply_deferred_waits()
         self.group_stream.wait_event(slot.walked)
-        check(lib().mirec_prepare_chunk_group(ctypes.byref(slot.prep),
-                                              self.group_stream.cuda_stream),
+        self._group_on(slot, self.group_stream)
+
+    def _group_on(self, slot, st):
+        check(lib().mirec_prepare_chunk_group(ctypes.byref(slot.prep), st.cuda_stream),
               'mirec_prepare_chunk_group')
-        slot.ready.record(self.group_stream)
+        slot.ready.record(st)
         slot.group_pending = False
 
     def _chunk_prep(self, slot):
         """The slot's mirec_chunk_prep descriptor (pointers fixed per slot)."""
-        cp = getattr(slot, 'prep', None)
-        if cp is not None:
-            return cp
-        from recbole_amd._native import ChunkPrep
+        if slot.prep is not None:
+            return slot.prep
         dev = self.device
         with torch.cuda.stream(self.prep_stream):   # a first call builds the used-id bitmap:
             walk = self.data.sampler.walk_args(dev)   # stream-ordered before the walk reads it
@@ -467,12 +464,11 @@ class FusedBPRTrainStep(object):
         cp.n_users, cp.n_items, cp.reject, cp.status = self.nU, self.nI, int(reject), p(status)
         cp.walk_ws, cp.walk_ws_bytes = self.samp_ws.data_ptr(), self.samp_ws.numel()
         cp.sort_ws, cp.sort_ws_bytes = self.sort_ws.data_ptr(), self.sort_ws.numel()
-        for tag in ('u', 'i'):
-            for f in ('perm', 'uniq', 'seg', 'nu'):
-                setattr(cp, f'{tag}_{f}', getattr(slot, f'{tag}_{f}').data_ptr())
-            if self.adam_mode == 'deferred':
-                setattr(cp, f'{tag}_ahead', getattr(slot, f'{tag}_ahead').data_ptr())
-                setattr(cp, f'{tag}_nah', getattr(slot, f'{tag}_nah').data_ptr())
+        for tag, l in zip('ui', slot.tab):
+            for f, x in (('perm', l.perm), ('uniq', l.uniq), ('seg', l.seg), ('nu', l.nu),
+                         ('ahead', l.ahead), ('nah', l.nah)):
+                if x is not None:
+                    setattr(cp, f'{tag}_{f}', x.data_ptr())
         if slot.records is not None:
             cp.u_rec, cp.u_crec, cp.i_rec, cp.i_crec = (r.data_ptr() for r in slot.records)
         spec = self._spec_ws()
@@ -482,10 +478,6 @@ class FusedBPRTrainStep(object):
         slot.prep = cp
         return cp
 
-    # K4s (mirec_sample_walk_spec): the chunk's walk by speculation (exact; two launches
-    # per 16 batches instead of a serial walk of ~10 us per batch)
-    SPEC_WALK = os.environ.get('MIREC_SPEC_WALK', '1') != '0'
-
     def _spec_ws(self):
         """Workspace of the speculative walk (shared by the slots: the walks run in
         order on the walk stream), or None where it does not apply."""
@@ -494,14 +486,13 @@ class FusedBPRTrainStep(object):
         T, Bc = self.times, self.Bg
         if Bc > 1024 or Bc * T > 4096:
             return None
-        ws = getattr(self, '_spec_buf', None)
-        if ws is None:
+        if self._spec_buf is None:
             counts = np.bincount(self._users.cpu().numpy(), minlength=self.nU)
             self._spec_stats = self.data.sampler.walk_stats(counts, Bc, T)
             n = lib().mirec_sample_walk_spec_workspace_size(Bc, T, min(self.C, 16),
                                                             *self._spec_stats)
-            ws = self._spec_buf = torch.empty(n, dtype=torch.uint8, device=self.device)
-        return ws
+            self._spec_buf = torch.empty(n, dtype=torch.uint8, device=self.device)
+        return self._spec_buf
 
     # ------------------------------------------------------------------ model side
     def _rec_ints(self, Bc):
@@ -515,21 +506,15 @@ class FusedBPRTrainStep(object):
 
     def _fill_tables(self):
         """Per-table pointers that do not depend on the batch."""
-        stU = self.opt.state[self.pU]
-        stI = self.opt.state[self.pI]
-        t = self._tables
-        t[0].p, t[0].m, t[0].v, t[0].n_rows = (self.pU.data_ptr(), stU['exp_avg'].data_ptr(),
-                                               stU['exp_avg_sq'].data_ptr(), self.nU)
-        t[1].p, t[1].m, t[1].v, t[1].n_rows = (self.pI.data_ptr(), stI['exp_avg'].data_ptr(),
-                                               stI['exp_avg_sq'].data_ptr(), self.nI)
-        t[0].dense_grad = t[1].dense_grad = None
-        if self.adam_mode == 'deferred':
-            t[0].last, t[1].last = self.lastU.data_ptr(), self.lastI.data_ptr()
-        else:
-            t[0].last = t[1].last = None
-        fs = getattr(self, 'fused_step', False)
-        t[0].p_alt = self.pU_alt.data_ptr() if fs else None
-        t[1].p_alt = self.pI_alt.data_ptr() if fs else None
+        deferred = self.adam_mode == 'deferred'
+        for t, p, n, last, alt in zip(self._tables, (self.pU, self.pI), (self.nU, self.nI),
+                                      (self.lastU, self.lastI), (self.pU_alt, self.pI_alt)):
+            st = self.opt.state[p]
+            t.p, t.m, t.v, t.n_rows = (p.data_ptr(), st['exp_avg'].data_ptr(),
+                                       st['exp_avg_sq'].data_ptr(), n)
+            t.dense_grad = None
+            t.last = last.data_ptr() if deferred else None
+            t.p_alt = alt.data_ptr() if self.fused_step else None
 
     def _adam_state(self):
         """(m, v, deferred step counts) of each table."""
@@ -547,113 +532,109 @@ class FusedBPRTrainStep(object):
         e1.record(stream)
         ev.append((name, e0, e1))
 
+    def _launch(self, name, stream, fn, *args):
+        """Kernel event `name`: the library's launcher `fn` with `args` on `stream`."""
+        self._record(name, stream,
+                     lambda: check(getattr(lib(), fn)(*args, stream.cuda_stream), fn))
+
+    def _sched(self, step_off):
+        """A K5 launcher's step arguments: optimizer step step_idx + step_off."""
+        return (self.consts.data_ptr(), self.step_idx.data_ptr(), step_off) + self._adam_args
+
+    @staticmethod
+    def _point_tables(t, lists, c, pers, ahead):
+        """Point the AdamTable descriptors `t` at batch c of each table's _Lists (blocks
+        of `pers` key slots per batch); `ahead`: with the look-ahead rows."""
+        for tq, l, per in zip(t, lists, pers):
+            tq.perm = l.perm.data_ptr() + 4 * c * per
+            tq.uniq = l.uniq.data_ptr() + 4 * c * per
+            tq.seg = l.seg.data_ptr() + 4 * c * (per + 1)
+            tq.n_uniq = l.nu.data_ptr() + 4 * c
+            tq.ahead_uniq = l.ahead.data_ptr() + 4 * c * per if ahead else None
+            tq.ahead_n_uniq = l.nah.data_ptr() + 4 * c if ahead else None
+
+    def _note_uniq(self, lists, c):
+        if self.kernel_events is not None:       # rows touched, for the bench's byte count
+            self.kernel_uniq.append(torch.stack([l.nu[c] for l in lists]))
+
     def _step(self, slot, c, Bc, stream, step_off, ahead):
         """Model-side work of global batch c of `slot` (Bc positives) as optimizer
         step step_idx + step_off; every pointer is relative to the slot or a
         persistent buffer (graph-capturable). `ahead`: batch c+1 of the slot runs
         next, so the deferred Adam also completes the rows it reads."""
-        T, d = self.times, self.d
-        KI = (1 + T) * Bc
-        L = lib()
-        st = stream.cuda_stream
-        sharded = self._sharded(Bc)
-        x0 = self.xbuf.data_ptr()
-        loss_p = self.loss_k.data_ptr() + 4 * c * self.Bg
-        user_g = slot.user_keys.data_ptr() + 8 * c * Bc      # the (global) batch
-        keys_g = slot.item_keys.data_ptr() + 8 * c * KI
-        gU, gI = x0, x0 + 4 * Bc * d
-        rowsU, rowsI = gU, gI
-        if sharded:
-            # K3 forward on the local slice -> [losses | coefficients] of this rank's
-            # block; all-gather; every rank rebuilds the global batch's gradient rows
-            lay, B = self.layout, self.B
-            user_p = slot.lu.data_ptr() + 8 * c * B
-            keys_p = slot.li.data_ptr() + 8 * c * (1 + T) * B
-            mine = self.xchg.data_ptr() + 4 * self.rank * lay.W
-
-            def bpr():
-                check(L.mirec_bpr_fwd_coef_f32(self.pU.data_ptr(), self.nU, self.pI.data_ptr(),
-                                               self.nI, d, user_p, keys_p, keys_p + 8 * B, B, T,
-                                               1e-10, self._grad_scale(Bc), mine,
-                                               mine + 4 * lay.coef0, st),
-                      'mirec_bpr_fwd_coef_f32')
-            self._record('bpr', stream, bpr)
-            self._record('exchange', stream, lambda: self._exchange(c))
-
-            def contrib():
-                check(L.mirec_bpr_contrib_f32(self.pU.data_ptr(), self.nU, self.pI.data_ptr(),
-                                              self.nI, d, user_g, keys_g, keys_g + 8 * Bc, Bc, T,
-                                              self.xchg.data_ptr() + 4 * lay.coef0, B, lay.W,
-                                              gU, gI, st), 'mirec_bpr_contrib_f32')
-            self._record('contrib', stream, contrib)
-        elif not self.fused_step:
-            def bpr():
-                check(L.mirec_bpr_fwd_bwd_f32(self.pU.data_ptr(), self.nU, self.pI.data_ptr(),
-                                              self.nI, d, user_g, keys_g, keys_g + 8 * Bc, Bc,
-                                              T, 1e-10, self._grad_scale(Bc), loss_p, None,
-                                              None, gU, gI, st), 'mirec_bpr_fwd_bwd_f32')
-            self._record('bpr', stream, bpr)
+        T = self.times
         t = self._tables
-        t[0].rows, t[1].rows = rowsU, rowsI
-        t[0].perm = slot.u_perm.data_ptr() + 4 * c * Bc
-        t[0].uniq = slot.u_uniq.data_ptr() + 4 * c * Bc
-        t[0].seg = slot.u_seg.data_ptr() + 4 * c * (Bc + 1)
-        t[0].n_uniq = slot.u_nu.data_ptr() + 4 * c
-        t[1].perm = slot.i_perm.data_ptr() + 4 * c * KI
-        t[1].uniq = slot.i_uniq.data_ptr() + 4 * c * KI
-        t[1].seg = slot.i_seg.data_ptr() + 4 * c * (KI + 1)
-        t[1].n_uniq = slot.i_nu.data_ptr() + 4 * c
-        if self.adam_mode == 'deferred' and ahead:
-            t[0].ahead_uniq = slot.u_ahead.data_ptr() + 4 * c * Bc
-            t[0].ahead_n_uniq = slot.u_nah.data_ptr() + 4 * c
-            t[1].ahead_uniq = slot.i_ahead.data_ptr() + 4 * c * KI
-            t[1].ahead_n_uniq = slot.i_nah.data_ptr() + 4 * c
+        gU = self.xbuf.data_ptr()                  # gradient rows: users, then items
+        t[0].rows, t[1].rows = gU, gU + 4 * Bc * self.d
+        self._point_tables(t, slot.tab, c, (Bc, (1 + T) * Bc),
+                           ahead and self.adam_mode == 'deferred')
+        users = slot.user_keys.data_ptr() + 8 * c * Bc       # the (global) batch's keys
+        items = slot.item_keys.data_ptr() + 8 * c * (1 + T) * Bc
+        keys = (users, items, items + 8 * Bc, Bc, T)         # users, positives, negatives
+        loss = (1e-10, self._grad_scale(Bc))                 # the BPR loss's gamma, 1 / rows
+        if self._dp_slice(Bc):
+            self._step_dp(slot, c, keys, loss, stream, step_off)
+        elif self.fused_step:
+            self._step_k35(slot, c, keys, loss, stream, step_off)
         else:
-            t[0].ahead_uniq = t[0].ahead_n_uniq = t[1].ahead_uniq = t[1].ahead_n_uniq = None
+            self._step_k3_k5(c, keys, loss, stream, step_off)
+        self._note_uniq(slot.tab, c)
 
-        if self.fused_step and not sharded:
-            # K35: BPR + touched-row Adam + look-ahead in one launch (no gradient rows),
-            # the touched rows from the chunk's records (built on the prep stream)
-            rec = [r.data_ptr() + 4 * c * w for r, w in zip(slot.records, self._rec_ints(Bc))]
-            rec += [x.data_ptr() for x in self._step_scratch]
+    def _params(self):
+        return self.pU.data_ptr(), self.nU, self.pI.data_ptr(), self.nI, self.d
 
-            def fused():
-                check(L.mirec_bpr_adam_step_f32(t, self._n_max, d, keys_g, Bc, T, 1e-10,
-                                                self._grad_scale(Bc), loss_p, *rec,
-                                                self.consts.data_ptr(),
-                                                self.step_idx.data_ptr(), step_off,
-                                                *self._adam_args, st), 'mirec_bpr_adam_step_f32')
-            self._record('step', stream, fused)
-            if self.kernel_events is not None:
-                self.kernel_uniq.append(torch.stack([slot.u_nu[c], slot.i_nu[c]]))
-            return
+    def _step_k35(self, slot, c, keys, loss, stream, step_off):
+        """K35: BPR + touched-row Adam + look-ahead in one launch (no gradient rows),
+        the touched rows from the chunk's records (built on the prep stream)."""
+        _, items, _, Bc, T = keys
+        rec = [r.data_ptr() + 4 * c * w for r, w in zip(slot.records, self._rec_ints(Bc))]
+        rec += [x.data_ptr() for x in self._step_scratch]
+        self._launch('step', stream, 'mirec_bpr_adam_step_f32', self._tables, self._n_max, self.d,
+                     items, Bc, T, *loss, self.loss_k.data_ptr() + 4 * c * self.Bg, *rec,
+                     *self._sched(step_off))
+
+    def _step_k3_k5(self, c, keys, loss, stream, step_off):
+        """K3 (losses + the batch's gradient rows), then K5 (Adam on the grouped rows)."""
+        t = self._tables
+        self._launch('bpr', stream, 'mirec_bpr_fwd_bwd_f32', *self._params(), *keys, *loss,
+                     self.loss_k.data_ptr() + 4 * c * self.Bg, None, None, t[0].rows, t[1].rows)
+        self._adam(stream, step_off)
+
+    def _step_dp(self, slot, c, keys, loss, stream, step_off):
+        """Replicated data parallelism: K3 forward on the local slice -> [losses |
+        coefficients] of this rank's block; all-gather; every rank rebuilds the global
+        batch's gradient rows (the arithmetic of K3); K5."""
+        T, B, lay, t = self.times, self.B, self.layout, self._tables
+        users = slot.lu.data_ptr() + 8 * c * B               # this rank's slice
+        items = slot.li.data_ptr() + 8 * c * (1 + T) * B
+        mine = self.xchg.data_ptr() + 4 * self.rank * lay.W
+        self._launch('bpr', stream, 'mirec_bpr_fwd_coef_f32', *self._params(), users, items,
+                     items + 8 * B, B, T, *loss, mine, mine + 4 * lay.coef0)
+        self._record('exchange', stream, lambda: self._exchange(c))
+        self._launch('contrib', stream, 'mirec_bpr_contrib_f32', *self._params(), *keys,
+                     self.xchg.data_ptr() + 4 * lay.coef0, B, lay.W, t[0].rows, t[1].rows)
+        self._adam(stream, step_off)
+
+    def _adam(self, stream, step_off, t=None, name='adam'):
+        """K5 on the rows the descriptors `t` (self._tables) point at, as step step_idx +
+        step_off."""
+        t = self._tables if t is None else t
         if self.adam_mode == 'deferred':
-            def adam():
-                check(L.mirec_adam_deferred_f32(t, 2, self._n_max, d, self.consts.data_ptr(),
-                                                self.step_idx.data_ptr(), step_off,
-                                                *self._adam_args, st), 'mirec_adam_deferred_f32')
+            self._launch(name, stream, 'mirec_adam_deferred_f32', t, 2, self._n_max, self.d,
+                         *self._sched(step_off))
         else:
-            def adam():
-                check(L.mirec_adam_multi_f32(t, 2, d, self.consts.data_ptr(),
-                                             self.step_idx.data_ptr(), step_off,
-                                             *self._adam_args, st), 'mirec_adam_multi_f32')
-        self._record('adam', stream, adam)
-        if self.kernel_events is not None:       # rows touched, for the bench's byte count
-            self.kernel_uniq.append(torch.stack([slot.u_nu[c], slot.i_nu[c]]))
+            self._launch(name, stream, 'mirec_adam_multi_f32', t, 2, self.d,
+                         *self._sched(step_off))
 
     def _exchange(self, c):
         """All-gather every rank's [losses | coefficients] block (RCCL over xGMI: 10 KB
-        per rank at C2), then lay the G*B losses out in global positive order for
-        chunk_finish."""
-        import torch.distributed as tdist
-        lay = self.layout
-        parts = list(self.xchg.view(self.G, lay.W).unbind(0))
-        if self._backend == 'nccl':            # RCCL: in place, one collective
-            tdist.all_gather_into_tensor(self.xchg, parts[self.rank], group=self.group)
-        else:                                  # gloo (CPU-staged; tests): list form
-            tdist.all_gather(parts, parts[self.rank].clone(), group=self.group)
+        per rank at C2, in place), then lay the G*B losses out in global positive order
+        for chunk_finish."""
+        from recbole_amd.trainer.dist import all_gather_blocks
+        blocks = self.xchg.view(self.G, self.layout.W)
+        all_gather_blocks(blocks, blocks[self.rank], self.group)
         self.loss_k[c * self.Bg:(c + 1) * self.Bg].view(self.G, self.B).copy_(
-            lay.gathered_losses(self.xchg))
+            self.layout.gathered_losses(self.xchg))
 
     def _finish(self, c0, n_steps, Bc, stream):
         """Losses of batches c0..c0+n_steps of the slot -> loss_hist; step_idx += n."""
@@ -669,24 +650,15 @@ class FusedBPRTrainStep(object):
         if self.adam_mode != 'deferred':
             return
         if rows is not None and any(r > 1 for r in rows):
-            rpw = (ctypes.c_int32 * 2)(*rows)
-
-            def flush():
-                check(lib().mirec_adam_flush_rows_f32(self._tables, 2, self.d, rpw,
-                                                      self.consts.data_ptr(),
-                                                      self.step_idx.data_ptr(), 0,
-                                                      *self._adam_args, stream.cuda_stream),
-                      'mirec_adam_flush_rows_f32')
+            self._launch('flush', stream, 'mirec_adam_flush_rows_f32', self._tables, 2, self.d,
+                         (ctypes.c_int32 * 2)(*rows), *self._sched(0))
         else:
-            def flush():
-                check(lib().mirec_adam_flush_f32(self._tables, 2, self.d, self.consts.data_ptr(),
-                                                 self.step_idx.data_ptr(), 0, *self._adam_args,
-                                                 stream.cuda_stream), 'mirec_adam_flush_f32')
-        self._record('flush', stream, flush)
+            self._launch('flush', stream, 'mirec_adam_flush_f32', self._tables, 2, self.d,
+                         *self._sched(0))
 
     def _entry_lists(self, slot):
         """(row list, device count) per table: the rows batch 0 of `slot` reads."""
-        return [(slot.u_uniq, slot.u_nu), (slot.i_uniq, slot.i_nu)]
+        return [(l.uniq, l.nu) for l in slot.tab]
 
     def _entry(self, slot, stream):
         """Deferred schedule, chunk entered without a flush before it: bring the
@@ -696,23 +668,18 @@ class FusedBPRTrainStep(object):
             return
         t = (AdamTable * 2)()                   # own descriptors: self._tables keeps its rows
         ctypes.memmove(t, self._tables, ctypes.sizeof(t))
-        for q, (uniq, n) in enumerate(self._entry_lists(slot)):
-            t[q].rows = self.xbuf.data_ptr()            # unused: no touched rows
-            t[q].perm = t[q].uniq = t[q].seg = uniq.data_ptr()
-            t[q].n_uniq = self.zero_i32.data_ptr()
-            t[q].ahead_uniq = uniq.data_ptr()
-            t[q].ahead_n_uniq = n.data_ptr()
-
-        def entry():
-            check(lib().mirec_adam_deferred_f32(t, 2, self._n_max, self.d, self.consts.data_ptr(),
-                                                self.step_idx.data_ptr(), -1, *self._adam_args,
-                                                stream.cuda_stream), 'mirec_adam_deferred_f32')
-        self._record('ahead', stream, entry)
+        # no touched rows (a zero count: the lists and `rows` are not read); the rows the
+        # batch reads as the look-ahead list
+        self._point_tables(t, [SimpleNamespace(perm=uniq, uniq=uniq, seg=uniq, nu=self.zero_i32,
+                                               ahead=uniq, nah=n)
+                               for uniq, n in self._entry_lists(slot)], 0, (0, 0), True)
+        t[0].rows = t[1].rows = self.xbuf.data_ptr()
+        self._adam(stream, -1, t, 'ahead')
 
     def _grad_scale(self, Bc):
         """1 / (rows of the GLOBAL batch): the reference's .mean() over the batch."""
         R = Bc * self.times
-        if getattr(self, '_gs_R', None) != R:
+        if self._gs_R != R:
             self._gs_R = R
             self._gs = float(np.float32(1.0) / np.float32(R))
         return self._gs
@@ -772,20 +739,20 @@ class FusedBPRTrainStep(object):
             raise RuntimeError('fused train step needs the train table on the GPU')
         self.n_batches = nb = math.ceil(self._users.numel() / self.Bg)
         table = self.opt.step_constants(self.opt.n_steps + 1, max(nb, 1)).reshape(-1)
+        ptrs = [(t.p, t.m, t.v) for t in self._tables]
+        self._fill_tables()                    # optimizer state may have been reloaded
+        stale = ptrs != [(t.p, t.m, t.v) for t in self._tables]
         if self.consts.numel() < table.size:   # persistent buffers (graph-captured pointers)
             self.consts = torch.zeros(table.size, dtype=torch.float32, device=self.device)
             self.loss_hist = torch.zeros(max(nb, 1), dtype=torch.float32, device=self.device)
-            for s in self.slots:
-                s.graphs = {}
-        ptrs = [(t.p, t.m, t.v) for t in self._tables]
-        self._fill_tables()                    # optimizer state may have been reloaded
-        if ptrs != [(t.p, t.m, t.v) for t in self._tables]:
-            for s in self.slots:
-                s.graphs = {}
+            stale = True
+        if stale:
+            self._drop_graphs()
         self.consts[:table.size].copy_(torch.from_numpy(table))
         self.loss_hist.zero_()
         self.step_idx.zero_()
-        self._busy0 = [t.n_rows for t in self._tables]   # rows that may lag (flush rows per wave)
+        n_rows = [t.n_rows for t in self._tables]
+        self._busy0 = n_rows                   # rows that may lag (flush rows per wave)
         self._batches_enqueued = 0
         if self.adam_mode == 'deferred':       # rows are all flushed: epoch-relative counts
             busy = []
@@ -798,9 +765,12 @@ class FusedBPRTrainStep(object):
             self.pU_alt.copy_(self.pU.data)    # zero-state row) valid in both
             self.pI_alt.copy_(self.pI.data)
         ramps = (0,) if hold_prep_from is None else (0, int(hold_prep_from))
-        self._plan, self._plan_starts = self._chunks(cuts, ramps), None
+        self._plan = chunk_plan.plan_chunks(self._users.numel(), self.Bg, self.C, self.RAMP,
+                                            cuts, ramps)
         self._flush_at = set(int(b) for b in flush_at)
-        self._flags = self._chunk_flags(self._plan)
+        self._flags = chunk_plan.chunk_flags(self._plan, self.Bg, self.FLUSH_EVERY,
+                                             self._flush_at, self.times, self.adam_mode, self.d,
+                                             n_rows, self._busy0, self.FLUSH_SPARSE_MAX_ROWS)
         if self.use_graph:                      # capture up front: capture synchronizes
             self._capture_variants()
         self.prep_stream.wait_stream(torch.cuda.current_stream(self.device))
@@ -813,7 +783,7 @@ class FusedBPRTrainStep(object):
         self._cur = None                       # chunk index being consumed
         for s in self.slots:
             s.free_recorded = False
-            if not self._sharded(self.Bg):     # the native preparation's descriptors now,
+            if not self._dp_slice(self.Bg):    # the native preparation's descriptors now,
                 self._chunk_prep(s)            # not on a timed region's first launch
         for _ in range(len(self.slots)):
             self._issue_prep()
@@ -830,7 +800,7 @@ class FusedBPRTrainStep(object):
                             else self._chunk_of(max(int(upto) - 1, 0)) + 1)
         if self._next_chunk < min(len(self._plan), self._prep_limit):
             k = self._next_chunk               # the first released walk starts right away:
-            if self.MAIN_FIRST and not self._sharded(self._plan[k][2]):
+            if self.MAIN_FIRST and not self._dp_slice(self._plan[k][2]):
                 # the whole preparation on the model's stream (no cross-queue hand-off
                 # before the first step); the next chunks' walks after its model launch
                 self._issue_prep(on=torch.cuda.current_stream(self.device))
@@ -864,7 +834,7 @@ class FusedBPRTrainStep(object):
             prev.free.record(stream)
             prev.free_recorded = True
         if (self.MAIN_FIRST and self._next_chunk == k and k < min(len(self._plan), self._prep_limit)
-                and not self._sharded(self._plan[k][2])):
+                and not self._dp_slice(self._plan[k][2])):
             self._issue_prep(on=stream)        # pipeline (re)start: prepared on this stream
             self._late_top_up = k
         while self._next_chunk <= k and self._next_chunk < min(len(self._plan),
@@ -882,7 +852,7 @@ class FusedBPRTrainStep(object):
         slot = self.slots[k % S]
         if self._late_top_up != k:
             self._top_up_prep(k)
-        if not getattr(slot, 'ready_on_model', False):
+        if not slot.ready_on_model:
             stream.wait_event(slot.ready)
         self._cur = k
 
@@ -891,7 +861,7 @@ class FusedBPRTrainStep(object):
         chunks replay their captured graph; a chunk entered mid-way (or timed with
         per-kernel events) launches eagerly, one step and one loss bookkeeping launch
         at a time. A chunk starts with the entry catch-up and ends with the flush
-        when its plan flags say so (_chunk_flags)."""
+        when its plan flags say so (chunk_plan.chunk_flags)."""
         stream = torch.cuda.current_stream(self.device)
         b = b_start
         while b < b_end:
@@ -933,16 +903,6 @@ class FusedBPRTrainStep(object):
         while self._next_chunk < lim:
             self._issue_prep()
 
-    def launch_batch(self, b):
-        self.run_batches(b, b + 1)
-
-    def _chunk_of(self, b):
-        """Index of the plan chunk holding global batch b."""
-        starts = self._plan_starts
-        if starts is None or len(starts) != len(self._plan):
-            starts = self._plan_starts = np.array([c[0] for c in self._plan], dtype=np.int64)
-        return max(int(np.searchsorted(starts, b, side='right')) - 1, 0)
-
     def sync_params(self):
         """Make the parameters current (deferred schedule: flush every row, unless
         the last enqueued work was a chunk's closing flush)."""
@@ -974,675 +934,15 @@ class FusedBPRTrainStep(object):
         """Drop the captured chunk graphs (they hold collectives of the process
         group: release them before torch.distributed.destroy_process_group)."""
         torch.cuda.synchronize(self.device)
+        self._drop_graphs()
+        torch.cuda.synchronize(self.device)
+
+    def _drop_graphs(self):
         for s in self.slots:
             s.graphs = {}
-        torch.cuda.synchronize(self.device)
 
 
-class ShardedBPRTrainStep(FusedBPRTrainStep):
-    """The fused pairwise step with ROW-SHARDED tables over G ranks:
-    rank r owns rows id % G == r of both tables (parameters, Adam m / v and the
-    deferred step counts) as a [S, d] shard, S = ceil(n / G).
-
-    Per optimizer step over a global batch of G*B positives (csrc/shard.hip):
-      prep (replicated on every rank, prep stream): walk + K2 grouping of the global
-        batch over owner-major keys, the exchange plans and this rank's slice of the
-        grouping (mirec_shard_plan / mirec_shard_own);
-      forward exchange: each owner gathers the rows every slice needs from its shards
-        (mirec_shard_gather_f32) and one all-to-all (RCCL over xGMI; equal blocks of
-        `cap` rows per rank pair) delivers them;
-      K3 on this rank's slice of positives, reading rows from the receive buffer;
-      backward exchange: the slice's per-slot gradient rows go back to the owners
-        in the same message positions (second all-to-all);
-      K5 (deferred) on the owned rows only, summing each row's contributions in the
-        global grouping order — the result is bit-identical to one GPU running the
-        global batch;
-      per chunk: one all-gather of the per-positive losses for the loss history.
-    The dominant optimizer work (touched rows + flush) is 1/G per rank. The model's
-    full parameter tensors are written back from the shards at end_epoch() (one
-    all-gather of p, m, v per epoch) for evaluation and checkpoints, and re-read
-    into the shards at begin_epoch(). With dist=None it runs the same protocol on
-    one rank (G = 1; the all-to-alls are copies)."""
-
-    CAP_SLACK = 1.25
-    # the per-step row exchanges: 'rccl' (two all-to-alls of equal blocks) or 'ipc' (the
-    # owners' gather stores into the readers' IPC-mapped windows, K3 stores the gradient
-    # rows into the owners' windows, flags on the GPU: csrc/comm.hip, trainer/comm.py)
-    EXCHANGE = os.environ.get('MIREC_EXCHANGE', 'rccl')
-
-    def __init__(self, model, optimizer, train_data, chunk=None, use_graph=True,
-                 adam_mode='deferred', dist=None, cap=None, exchange=None):
-        if adam_mode != 'deferred':
-            raise ValueError('the row-sharded step runs the deferred Adam schedule')
-        exchange = exchange or self.EXCHANGE
-        if exchange not in ('rccl', 'ipc'):
-            raise ValueError(f"exchange must be 'rccl' or 'ipc', got {exchange!r}")
-        super().__init__(model, optimizer, train_data, chunk=chunk, use_graph=use_graph,
-                         adam_mode=adam_mode, dist=dist, fused_step=False)
-        G, B, T, d, dev = self.G, self.B, self.times, self.d, self.device
-        self.SU, self.SI = -(-self.nU // G), -(-self.nI // G)
-        # rows per (slice, owner) message: the slice's (2+T)*B slots spread over G
-        # owners (cyclic ownership); a chunk whose plan overflows is re-planned with a
-        # larger cap before it runs (_enter_chunk), never run on a truncated plan
-        self.cap = int(cap or min((2 + T) * B,
-                                  math.ceil(self.CAP_SLACK * (2 + T) * B / G) + 64))
-        self.shU = [torch.zeros(self.SU, d, device=dev) for _ in range(3)]   # p, m, v
-        self.shI = [torch.zeros(self.SI, d, device=dev) for _ in range(3)]
-        self.lastU = torch.zeros(self.SU, dtype=torch.int32, device=dev)
-        self.lastI = torch.zeros(self.SI, dtype=torch.int32, device=dev)
-        self._solo = dist is None            # one rank, no process group: no collectives
-        self.exchange = 'rccl' if self._solo else exchange
-        self.win = None
-        if self.exchange == 'ipc':           # every rank's receive window, mapped everywhere
-            from recbole_amd.trainer.comm import PeerWindows
-            self.win = PeerWindows(dist, (2 + T) * B, d, dev)
-        self.loss_g = torch.empty(G * self.C * B, dtype=torch.float32, device=dev)
-        self.loss_mine = torch.zeros(self.C * B, dtype=torch.float32, device=dev)
-        self.status = torch.zeros(2, dtype=torch.int32, device=dev)    # epoch backstop
-        self.cap_growths = 0
-        Bg, KI = self.Bg, (1 + T) * self.Bg
-        C = self.C
-        for sl in self.slots:
-            sl.u_keyed = torch.empty(C * Bg, dtype=torch.int64, device=dev)
-            sl.i_keyed = torch.empty(C * KI, dtype=torch.int64, device=dev)
-            sl.map2 = torch.empty(C * (Bg + KI), dtype=torch.int32, device=dev)
-            sl.pos = torch.empty(C * (2 + T) * B, dtype=torch.int64, device=dev)
-            # this chunk's plan status ([overflow, largest message]), read by the host
-            # before the chunk's model side is launched (_enter_chunk)
-            sl.plan_status = torch.zeros(4, dtype=torch.int32, device=dev)
-            sl.plan_status_host = torch.zeros(4, dtype=torch.int32).pin_memory()
-            sl.planned = torch.cuda.Event()
-            for tag, per in (('u', Bg), ('i', KI)):
-                setattr(sl, f'own_{tag}', torch.empty(C * per, dtype=torch.int32, device=dev))
-                setattr(sl, f'own_{tag}_seg', torch.empty(C * (per + 1), dtype=torch.int32,
-                                                          device=dev))
-                setattr(sl, f'own_{tag}_n', torch.zeros(C, dtype=torch.int32, device=dev))
-                setattr(sl, f'perm2_{tag}', torch.empty(C * per, dtype=torch.int32, device=dev))
-                setattr(sl, f'own_{tag}_ah', torch.empty(C * per, dtype=torch.int32, device=dev))
-                setattr(sl, f'own_{tag}_nah', torch.zeros(C, dtype=torch.int32, device=dev))
-                setattr(sl, f'sel_{tag}', torch.empty(C * per, dtype=torch.int32, device=dev))
-                if self.win is not None:     # the owner's push lists (mirec_shard_next)
-                    setattr(sl, f'next_{tag}_t', torch.empty(C * per, dtype=torch.int32,
-                                                             device=dev))
-                    setattr(sl, f'next_{tag}_a', torch.empty(C * per, dtype=torch.int32,
-                                                             device=dev))
-        # slots per (batch, table) a rank's owner-filtered grouping holds (its ~1/G share
-        # of the global batch with slack; a batch over it is re-selected at the table's
-        # full size before its chunk runs: _enter_chunk)
-        self.cap_sel = {tag: min(per, math.ceil(self.CAP_SLACK * per / G) + 64)
-                        for tag, per in (('u', Bg), ('i', KI))}
-        self.sel_growths = 0
-        self._alloc_exchange()
-        self._n_max = (ctypes.c_int64 * 2)(min(Bg, self.SU), min(KI, self.SI))
-        self._fill_tables()
-
-    def _alloc_exchange(self):
-        """Buffers sized by `cap`: the two all-to-all send / receive buffers (rccl; the
-        ipc exchange receives in the windows, sized for the largest cap) and the per-slot
-        message plans."""
-        M, d, dev = self.G * self.cap, self.d, self.device
-        if self.win is None:
-            self.sendF = torch.empty(M, d, device=dev)
-            self.recvF = self.sendF if self._solo else torch.empty(M, d, device=dev)
-            self.sendB = torch.empty(M, d, device=dev)
-            self.recvB = self.sendB if self._solo else torch.empty(M, d, device=dev)
-        for sl in self.slots:
-            sl.fwd_rows = torch.empty(self.C * M, dtype=torch.int64, device=dev)
-            sl.bwd_src = torch.empty(self.C * M, dtype=torch.int32, device=dev)
-
-    # ------------------------------------------------------------ shards <-> full tensors
-    def _owned_ids(self, n, S):
-        ids = torch.arange(S, device=self.device, dtype=torch.int64) * self.G + self.rank
-        return ids[ids < n]
-
-    def _load_shards(self):
-        """Owned rows of the model's full p and the optimizer's m, v -> the shards."""
-        full = [(self.pU, self.opt.state[self.pU]), (self.pI, self.opt.state[self.pI])]
-        for (p, st), sh, n, S in zip(full, (self.shU, self.shI), (self.nU, self.nI),
-                                     (self.SU, self.SI)):
-            ids = self._owned_ids(n, S)
-            for dst, src in zip(sh, (p.data, st['exp_avg'], st['exp_avg_sq'])):
-                dst[:ids.numel()].copy_(src[ids])
-
-    def _store_shards(self):
-        """All shards -> the full p, m, v on every rank (one all-gather each)."""
-        full = [(self.pU, self.opt.state[self.pU]), (self.pI, self.opt.state[self.pI])]
-        for (p, st), sh, n, S in zip(full, (self.shU, self.shI), (self.nU, self.nI),
-                                     (self.SU, self.SI)):
-            for src, dst in zip(sh, (p.data, st['exp_avg'], st['exp_avg_sq'])):
-                g = self._all_gather(src)                       # [G*S, d], owner-major
-                dst.copy_(g.view(self.G, S, self.d).transpose(0, 1).reshape(-1, self.d)[:n])
-
-    def _all_gather(self, x):
-        if self.group is None:
-            return x
-        import torch.distributed as tdist
-        out = torch.empty((self.G,) + tuple(x.shape), dtype=x.dtype, device=x.device)
-        if self._backend == 'nccl':
-            tdist.all_gather_into_tensor(out, x.contiguous(), group=self.group)
-        else:
-            parts = list(out.unbind(0))
-            tdist.all_gather(parts, x.contiguous(), group=self.group)
-        return out.view((-1,) + tuple(x.shape[1:]))
-
-    def _all_to_all(self, recv, send):
-        if self.group is None:
-            return                                              # recv is send
-        import torch.distributed as tdist
-        if self._backend == 'nccl':
-            tdist.all_to_all_single(recv, send, group=self.group)
-        else:                                                   # gloo: host-staged
-            r = torch.empty(recv.shape, dtype=recv.dtype)
-            tdist.all_to_all_single(r, send.cpu(), group=self.group)
-            recv.copy_(r)
-
-    # ------------------------------------------------------------ data side
-    def _prepare(self, slot, chunk, on=None):     # on: the base class's diagnostic (unused)
-        b0, nb, Bc = chunk
-        T, G, r = self.times, self.G, self.rank
-        KI = (1 + T) * Bc
-        L = lib()
-        if slot.free_recorded:
-            self.prep_stream.wait_event(slot.free)
-        with torch.cuda.stream(self.prep_stream):
-            st = self.prep_stream.cuda_stream
-            s0 = b0 * self.Bg
-            users = slot.user_keys[:nb * Bc]
-            users.copy_(self._users[s0:s0 + nb * Bc])
-            keys = slot.item_keys[:nb * KI].view(nb, 1 + T, Bc)
-            keys[:, 0, :].copy_(self._items[s0:s0 + nb * Bc].view(nb, Bc))
-            neg = slot.item_keys[Bc:nb * KI]
-            self.data.sampler.launch_batches(users, Bc, nb, T, neg, out_stride=KI,
-                                             ws=self.samp_ws)
-            self._plan_chunk(slot, chunk, st)
-            slot.ready.record(self.prep_stream)
-        slot.chunk = chunk
-
-    def _plan_chunk(self, slot, chunk, st):
-        """This rank's grouping of a walked chunk and its exchange plans (on the current
-        stream, `st`): per table, the slots of the rows this rank owns (mirec_shard_select,
-        ~1/G of the global batch), their K2 grouping over owner-major keys and look-ahead
-        lists; the plans from the unsorted keys (mirec_shard_plan); the owned lists with the
-        contributions' places in the backward messages (mirec_shard_own_sel). The plan
-        status goes to pinned host memory."""
-        _, nb, Bc = chunk
-        T, G, r = self.times, self.G, self.rank
-        KI = (1 + T) * Bc
-        L = lib()
-        users = slot.user_keys[:nb * Bc]
-        items = slot.item_keys[:nb * KI]
-        slot.plan_status.zero_()
-        cs = {}
-        for k, (tag, ids, per, S) in enumerate((('u', users, Bc, self.SU),
-                                                ('i', items, KI, self.SI))):
-            cs[tag] = c_ = min(self.cap_sel[tag], per)
-            keyed = getattr(slot, f'{tag}_keyed')[:nb * c_]
-            check(L.mirec_shard_select(ids.data_ptr(), nb, per, G, S, r, c_, keyed.data_ptr(),
-                                       getattr(slot, f'sel_{tag}').data_ptr(),
-                                       slot.plan_status.data_ptr() + 4 * (2 + k), st),
-                  'mirec_shard_select')
-            g_ = lambda n: getattr(slot, f'{tag}_{n}')
-            self.sort_ws = ops.segment_sort_batched(keyed, c_, G * S + 1, g_('perm'), g_('uniq'),
-                                                    g_('seg'), g_('nu'), ws=self.sort_ws)
-            ops.uniq_ahead_diff(g_('uniq'), g_('nu'), c_, nb, g_('ahead'), g_('nah'))
-        check(L.mirec_shard_plan(users.data_ptr(), items.data_ptr(), nb, Bc, self.B, T, G, r,
-                                 self.cap, slot.fwd_rows.data_ptr(), slot.map2.data_ptr(),
-                                 slot.pos.data_ptr(), slot.bwd_src.data_ptr(),
-                                 slot.plan_status.data_ptr(), st), 'mirec_shard_plan')
-        for tag, per, off, S in (('u', Bc, 0, self.SU), ('i', KI, Bc, self.SI)):
-            g_ = lambda n: getattr(slot, n).data_ptr()
-            check(L.mirec_shard_own_sel(g_(f'{tag}_uniq'), g_(f'{tag}_seg'), g_(f'{tag}_nu'),
-                                        g_(f'{tag}_perm'), cs[tag], nb, g_(f'{tag}_ahead'),
-                                        g_(f'{tag}_nah'), slot.map2.data_ptr(), Bc + KI, off,
-                                        S, r, g_(f'sel_{tag}'), per, g_(f'own_{tag}'),
-                                        g_(f'own_{tag}_seg'), g_(f'own_{tag}_n'),
-                                        g_(f'perm2_{tag}'), g_(f'own_{tag}_ah'),
-                                        g_(f'own_{tag}_nah'), st), 'mirec_shard_own_sel')
-            if self.win is not None:
-                check(L.mirec_shard_next(g_(f'own_{tag}'), g_(f'own_{tag}_n'),
-                                         g_(f'own_{tag}_ah'), g_(f'own_{tag}_nah'), per, nb,
-                                         g_(f'next_{tag}_t'), g_(f'next_{tag}_a'), st),
-                      'mirec_shard_next')
-        # epoch backstop: overflow flag (min: -4 < 0) and the largest message (max)
-        torch.minimum(self.status[:1], slot.plan_status[:1], out=self.status[:1])
-        torch.maximum(self.status[1:], slot.plan_status[1:2], out=self.status[1:])
-        slot.plan_status_host.copy_(slot.plan_status, non_blocking=True)
-        slot.planned.record(torch.cuda.current_stream(self.device))
-
-    def _enter_chunk(self, k, stream):
-        """Before chunk k's model side is enqueued: its plan must fit `cap`. Every rank
-        counts every message, so all ranks see the same status and grow `cap` to the
-        same value (no collective); the chunk and the prepared ones after it are
-        re-planned. No step ever runs on an overflowed plan."""
-        new = self._cur != k
-        super()._enter_chunk(k, stream)
-        if not new:
-            return
-        slot = self.slots[k % len(self.slots)]
-        if not slot.planned.query():          # the plan status reaches pinned memory
-            slot.planned.synchronize()
-        over, most, sel_u, sel_i = (int(x) for x in slot.plan_status_host)
-        _, _, Bc = self._plan[k]
-        grow = {tag: n for tag, n, per in (('u', sel_u, Bc), ('i', sel_i, (1 + self.times) * Bc))
-                if n > min(self.cap_sel[tag], per)}
-        if grow:
-            self._grow_sel(grow)
-            over, most = (int(x) for x in slot.plan_status_host[:2])
-        if over == -4:
-            self._grow_cap(most)
-
-    def _grow_sel(self, grow):
-        """A batch owns more slots of a table than its owner-filtered grouping holds:
-        re-select + re-plan every prepared chunk with that table's full batch size (no
-        overflow possible). The graphs stay (they read the owned lists, whose strides do
-        not change)."""
-        T, Bg = self.times, self.Bg
-        logging.getLogger().warning(f'owner-filtered grouping: {grow} owned slots exceed '
-                                    f'cap_sel={self.cap_sel}; re-selecting at full size')
-        torch.cuda.synchronize(self.device)
-        for tag in grow:
-            self.cap_sel[tag] = Bg if tag == 'u' else (1 + T) * Bg
-        self.sel_growths += 1
-        for q in range(self._cur if self._cur is not None else 0, self._next_chunk):
-            slot = self.slots[q % len(self.slots)]
-            with torch.cuda.stream(self.prep_stream):
-                self._plan_chunk(slot, self._plan[q], self.prep_stream.cuda_stream)
-        torch.cuda.synchronize(self.device)
-
-    def _grow_cap(self, most):
-        """Larger messages: reallocate the cap-sized buffers, re-plan every prepared
-        chunk from its walked keys and recapture the chunk graphs."""
-        T, B = self.times, self.B
-        new_cap = min((2 + T) * B, max(most, math.ceil(self.CAP_SLACK * self.cap)))
-        logger = logging.getLogger()
-        logger.warning(f'row exchange: a (slice, owner) message of {most} rows exceeds '
-                       f'cap={self.cap}; re-planning with cap={new_cap}')
-        torch.cuda.synchronize(self.device)
-        self.cap = new_cap
-        self.cap_growths += 1
-        self._alloc_exchange()
-        self._fill_tables()
-        self.status.zero_()
-        for q in range(self._cur, self._next_chunk):           # prepared chunks, in order
-            slot = self.slots[q % len(self.slots)]
-            with torch.cuda.stream(self.prep_stream):
-                self._plan_chunk(slot, self._plan[q], self.prep_stream.cuda_stream)
-        torch.cuda.synchronize(self.device)
-        if int(self.slots[self._cur % len(self.slots)].plan_status_host[0]) == -4:
-            raise RuntimeError('row exchange plan still overflows after re-planning')
-        for slot in self.slots:                                 # later chunks: checked on entry
-            slot.graphs = {}
-        if self.use_graph:
-            self._capture_variants()
-
-    # ------------------------------------------------------------ model side
-    def _fill_tables(self):
-        if not hasattr(self, 'shU'):
-            return super()._fill_tables()
-        t = self._tables
-        for q, (sh, last, S) in enumerate(((self.shU, self.lastU, self.SU),
-                                           (self.shI, self.lastI, self.SI))):
-            t[q].p, t[q].m, t[q].v = (x.data_ptr() for x in sh)
-            t[q].n_rows = S
-            t[q].last = last.data_ptr()
-            t[q].dense_grad = None
-            t[q].rows = self.win.bwd if self.win is not None else self.recvB.data_ptr()
-
-    def _adam_state(self):
-        return [(self.shU[1], self.shU[2], self.lastU), (self.shI[1], self.shI[2], self.lastI)]
-
-    def _entry_lists(self, slot):
-        return [(slot.own_u, slot.own_u_n), (slot.own_i, slot.own_i_n)]
-
-    def _n_local(self, Bc):
-        return max(0, min(self.B, Bc - self.rank * self.B))
-
-    def _step_ipc(self, slot, c, Bc, stream):
-        """The forward half of a step through the peer windows (csrc/comm.hip). The chunk's
-        first step pushes its rows with a gather launch (after the entry catch-up); later
-        steps' rows were pushed by the step before's optimizer launch (_adam_ipc). K3's
-        blocks wait for the owners' flags on the GPU (no separate wait launch), read the
-        rows in the window and store each gradient row into its owner's window."""
-        T, B = self.times, self.B
-        L = lib()
-        st = stream.cuda_stream
-        n = self._n_local(Bc)
-        w = self.win.comm
-        if c == 0:
-            def push():
-                check(L.mirec_comm_push_rows_f32(w, self.shU[0].data_ptr(),
-                                                 self.shI[0].data_ptr(), slot.fwd_rows.data_ptr(),
-                                                 self.cap, st), 'mirec_comm_push_rows_f32')
-            self._record('gather', stream, push)
-        loss_p = self.loss_mine.data_ptr() + 4 * c * B
-        pos_p = slot.pos.data_ptr() + 8 * c * (2 + T) * B
-
-        def bpr():                      # every rank launches it: its last block raises the flags
-            check(L.mirec_comm_bpr_f32(w, pos_p, pos_p + 8 * n, pos_p + 16 * n, n, T, 1e-10,
-                                       self._grad_scale(Bc), loss_p, self.cap, st),
-                  'mirec_comm_bpr_f32')
-        self._record('bpr', stream, bpr)
-
-    def _adam_ipc(self, slot, c, Bc, stream, step_off, ahead):
-        """The owner's deferred Adam with the backward wait and, unless c is the chunk's
-        last step, the next step's forward push folded in (mirec_comm_adam_deferred_f32):
-        every row step c+1 reads is in this launch's touched or look-ahead list, and goes
-        from registers to its readers' windows right after its update."""
-        KI = (1 + self.times) * Bc
-        t = self._tables
-        nxt = seg = dst = None
-        if ahead:
-            g_ = lambda n, off: getattr(slot, n).data_ptr() + 4 * off
-            nxt = (ctypes.c_void_p * 4)(g_('next_u_t', c * Bc), g_('next_u_a', c * Bc),
-                                        g_('next_i_t', c * KI), g_('next_i_a', c * KI))
-            seg = (ctypes.c_void_p * 2)(g_('own_u_seg', (c + 1) * (Bc + 1)),
-                                        g_('own_i_seg', (c + 1) * (KI + 1)))
-            dst = (ctypes.c_void_p * 2)(g_('perm2_u', (c + 1) * Bc), g_('perm2_i', (c + 1) * KI))
-        st = stream.cuda_stream
-
-        def adam():
-            check(lib().mirec_comm_adam_deferred_f32(
-                self.win.comm, t, 2, self._n_max, self.d, self.consts.data_ptr(),
-                self.step_idx.data_ptr(), step_off, *self._adam_args, nxt, seg, dst, self.cap, st),
-                'mirec_comm_adam_deferred_f32')
-        self._record('adam', stream, adam)
-
-    def _step(self, slot, c, Bc, stream, step_off, ahead):
-        T, d, G, B, M = self.times, self.d, self.G, self.B, self.G * self.cap
-        KI = (1 + T) * Bc
-        L = lib()
-        st = stream.cuda_stream
-        n = self._n_local(Bc)
-        if self.win is not None:
-            self._step_ipc(slot, c, Bc, stream)
-        else:
-            self._step_rccl(slot, c, Bc, stream)
-        t = self._tables
-        for q, (tag, per) in enumerate((('u', Bc), ('i', KI))):
-            t[q].perm = getattr(slot, f'perm2_{tag}').data_ptr() + 4 * c * per
-            t[q].uniq = getattr(slot, f'own_{tag}').data_ptr() + 4 * c * per
-            t[q].seg = getattr(slot, f'own_{tag}_seg').data_ptr() + 4 * c * (per + 1)
-            t[q].n_uniq = getattr(slot, f'own_{tag}_n').data_ptr() + 4 * c
-            if ahead:
-                t[q].ahead_uniq = getattr(slot, f'own_{tag}_ah').data_ptr() + 4 * c * per
-                t[q].ahead_n_uniq = getattr(slot, f'own_{tag}_nah').data_ptr() + 4 * c
-            else:
-                t[q].ahead_uniq = t[q].ahead_n_uniq = None
-
-        if self.win is not None:
-            self._adam_ipc(slot, c, Bc, stream, step_off, ahead)
-        else:
-            def adam():
-                check(L.mirec_adam_deferred_f32(t, 2, self._n_max, d, self.consts.data_ptr(),
-                                                self.step_idx.data_ptr(), step_off,
-                                                *self._adam_args, st), 'mirec_adam_deferred_f32')
-            self._record('adam', stream, adam)
-        if self.kernel_events is not None:
-            self.kernel_uniq.append(torch.stack([slot.own_u_n[c], slot.own_i_n[c]]))
-
-    def _step_rccl(self, slot, c, Bc, stream):
-        T, d, G, B, M = self.times, self.d, self.G, self.B, self.G * self.cap
-        L = lib()
-        st = stream.cuda_stream
-        n = self._n_local(Bc)
-
-        def fwd_gather():
-            check(L.mirec_shard_gather_f32(self.shU[0].data_ptr(), self.shI[0].data_ptr(), d,
-                                           slot.fwd_rows.data_ptr() + 8 * c * M, M,
-                                           self.sendF.data_ptr(), st), 'mirec_shard_gather_f32')
-        self._record('gather', stream, fwd_gather)
-        self._record('exchange', stream, lambda: self._all_to_all(self.recvF, self.sendF))
-        loss_p = self.loss_mine.data_ptr() + 4 * c * B
-        pos_p = slot.pos.data_ptr() + 8 * c * (2 + T) * B
-
-        def bpr():
-            # K3 reading the received rows; each slot's gradient row goes straight into
-            # its backward message position (the position its row came in): no separate
-            # backward gather (sendB's padding rows are never read by the owners)
-            if n == 0:
-                return
-            check(L.mirec_bpr_fwd_bwd_at_ids_f32(self.recvF.data_ptr(), M, d, pos_p,
-                                                 pos_p + 8 * n, pos_p + 16 * n, n, T, 1e-10,
-                                                 self._grad_scale(Bc), loss_p,
-                                                 self.sendB.data_ptr(), st),
-                  'mirec_bpr_fwd_bwd_at_ids_f32')
-        self._record('bpr', stream, bpr)
-        self._record('exchange_bwd', stream, lambda: self._all_to_all(self.recvB, self.sendB))
-
-    def _finish(self, c0, n_steps, Bc, stream):
-        """Losses of this rank's slices of steps c0..c0+n_steps -> all ranks (one
-        all-gather), laid out in global positive order, then chunk_finish."""
-        B, G = self.B, self.G
-        mine = self.loss_mine[c0 * B:(c0 + n_steps) * B]
-        gathered = self._all_gather(mine).view(G, n_steps, B)
-        self.loss_k.view(self.C, self.Bg)[c0:c0 + n_steps].view(n_steps, G, B).copy_(
-            gathered.transpose(0, 1))
-        super()._finish(c0, n_steps, Bc, stream)
-
-    # ------------------------------------------------------------ epoch API
-    def begin_epoch(self, cuts=(), hold_prep_from=None, flush_at=()):
-        self.status.zero_()
-        self._load_shards()
-        return super().begin_epoch(cuts=cuts, hold_prep_from=hold_prep_from, flush_at=flush_at)
-
-    def close(self):
-        super().close()
-        if self.win is not None:             # after a barrier: no rank still stores into it
-            self.win.close()
-            self.win = None
-
-    def end_epoch(self, n_done=None):
-        losses = super().end_epoch(n_done)
-        if self.win is not None and self.win.status() != 0:
-            raise RuntimeError('row exchange: a wait for a peer\'s flags timed out (a rank '
-                               'stopped or fell out of step)')
-        if int(self.status[0].item()) == -4:                 # backstop: _enter_chunk re-plans
-            raise RuntimeError(f'row exchange overflow: a (slice, owner) message exceeded '
-                               f'cap={self.cap} rows')
-        self._store_shards()
-        return losses
-
-
-def fused_full_sort_eval(model, eval_data, topk_evaluator, user_batch=1 << 20, dp=None,
-                         round_users=None):
-    """Trainer.evaluate for a FULL loader (trainer.py:355-412) on K6: scores,
-    pad/history mask, top-K and positive flags in one kernel per user batch; only
-    the [n_users, K] positive matrix returns to the host for the metric
-    reduction (evaluators.py:122-141). With a DataParallelStep `dp` every rank ranks
-    its contiguous block of users and one all-gather assembles the flags in user
-    order (trainer/dist.py) — the metrics of one GPU."""
-    dev = model.fused_item_table().device
-    K = max(topk_evaluator.topk)
-    uids, hist_ptr, hist_cols, pos_ptr, pos_cols = eval_data.device_csr(dev)
-    EI = model.fused_item_table().contiguous()
-    n = uids.numel()
-    lo, hi, blk = dp.user_block(n) if dp is not None else (0, n, n)
-    flags = torch.empty(max(hi - lo, 0), K, dtype=torch.uint8, device=dev)
-    rnd = round_users or _fullsort_round_users(dev, EI.shape[1])
-    if dp is None and n > rnd and user_batch >= n and round_users != 0 and K >= 2:
-        return _fullsort_overlapped(model, eval_data, topk_evaluator, uids, hist_ptr, hist_cols,
-                                    pos_ptr, pos_cols, EI, K, flags, rnd)
-    for s in range(lo, hi, user_batch):
-        e = min(hi, s + user_batch)
-        Uq = model.fused_user_vectors(uids[s:e]).contiguous()
-        o = {'pos_flags': flags[s - lo:e - lo]}
-        ops.fullsort_topk(Uq, EI, K, hist_ptr=hist_ptr[s:e + 1], hist_cols=hist_cols,
-                          pos_ptr=pos_ptr[s:e + 1], pos_cols=pos_cols, out=o)
-    if dp is not None:
-        flags = dp.gather_rows(flags, n, blk)
-    pos_idx = flags.cpu().numpy().astype(bool)
-    return topk_evaluator.evaluate_pos_idx(pos_idx, eval_data.get_pos_len_list())
-
-
-def _fullsort_round_users(dev, d):
-    """Users of one full round of K6 workgroups (128 users each; two resident per
-    CU for d <= 128, one for d = 256): launches of this size fill the chip."""
-    cus = torch.cuda.get_device_properties(dev).multi_processor_count
-    return 128 * cus * (2 if d <= 128 else 1)
-
-
-def _fullsort_overlapped(model, eval_data, topk_evaluator, uids, hist_ptr, hist_cols, pos_ptr,
-                         pos_cols, EI, K, flags, chunk):
-    """fused_full_sort_eval in round-sized K6 launches: each launch's flags go to the
-    host on a copy stream and its metric rows are reduced while the next launches
-    run (TopKEvaluator.evaluate_pos_idx_chunks: the same values as one block)."""
-    dev = flags.device
-    n = uids.numel()
-    host = torch.empty(flags.shape, dtype=torch.uint8, pin_memory=True)
-    copy_stream = torch.cuda.Stream(device=dev)
-    done = []
-    for s in range(0, n, chunk):
-        e = min(n, s + chunk)
-        Uq = model.fused_user_vectors(uids[s:e]).contiguous()
-        # a launch far below a round (the last one) splits the item range instead,
-        # so it does not take a full round's time for a few workgroups
-        wgs, full = -(-(e - s) // 128), chunk // 128
-        split = min(16, full // wgs) if 2 * wgs <= full else 1
-        ops.fullsort_topk(Uq, EI, K, hist_ptr=hist_ptr[s:e + 1], hist_cols=hist_cols,
-                          pos_ptr=pos_ptr[s:e + 1], pos_cols=pos_cols,
-                          out={'pos_flags': flags[s:e]}, n_split=split)
-        ready = torch.cuda.Event()
-        ready.record()
-        with torch.cuda.stream(copy_stream):
-            copy_stream.wait_event(ready)
-            host[s:e].copy_(flags[s:e], non_blocking=True)
-            copied = torch.cuda.Event()
-            copied.record(copy_stream)
-        done.append((s, e, copied, Uq))
-    pl = np.asarray(eval_data.get_pos_len_list())
-
-    def blocks():
-        for s, e, copied, _ in done:
-            copied.synchronize()
-            yield host[s:e].numpy().astype(bool), pl[s:e]
-    out = topk_evaluator.evaluate_pos_idx_chunks(blocks(), n)
-    torch.cuda.current_stream(dev).wait_stream(copy_stream)
-    return out
-
-
-def fused_seq_full_sort_eval(model, eval_data, topk_evaluator):
-    """Trainer.evaluate for SequentialFullDataLoader (trainer.py:328-353 with
-    sequential_dataloader.py:318-345: pad column masked, the target swapped to
-    the front, no history mask) on K6: per batch, the sequence representations
-    are ranked against every item with the target as the only positive."""
-    dev = model.fused_item_table().device
-    K = max(topk_evaluator.topk)
-    EI = model.fused_item_table().contiguous()
-    flags = []
-    for interaction, _, _, _, _ in eval_data:
-        inter = interaction.to(dev)
-        Uq = model.fused_query_vectors(inter).detach().contiguous()
-        n = Uq.shape[0]
-        pos_ptr = torch.arange(n + 1, dtype=torch.int64, device=dev)
-        pos_cols = inter[eval_data.iid_field].to(torch.int32).contiguous()
-        o = ops.fullsort_topk(Uq, EI, K, pos_ptr=pos_ptr, pos_cols=pos_cols)
-        flags.append(o['pos_flags'])
-    pos_idx = torch.cat(flags).cpu().numpy().astype(bool)
-    return topk_evaluator.evaluate_pos_idx(pos_idx, eval_data.get_pos_len_list())
-
-
-def fused_seq_sampled_eval(model, eval_data, topk_evaluator):
-    """Trainer.evaluate for SequentialNegSampleDataLoader in evaluation (uni-N, this
-    fork's validation, data/utils.py:86-88): the reference repeats every sequence
-    1+N times through the whole model (predict on each copy) and ranks the padded
-    score rows with topk (trainer.py:384-409, abstract_evaluator.py:65-75). Here each
-    sequence is encoded once and K9c counts the sampled items that beat the
-    positive; pos_idx[q, r] = (rank[q] == r). The negatives are the ones the
-    RepeatableSampler's per-row walk would draw (sample_by_user_ids(uid, N) for row
-    after row, no rejection): the next N values of the walk, row by row, taken with
-    one device gather; the walk pointer advances by rows x N exactly as it would."""
-    from recbole_amd._native import check, lib, ptr, stream_handle
-    sampler = eval_data.sampler
-    dev = model.fused_item_table().device
-    EI = model.fused_item_table().contiguous()
-    K = max(topk_evaluator.topk)
-    m = eval_data.neg_sample_by
-    sampler.to_device(dev)
-    L = sampler.random_list_length
-    ranks = []
-    for start in range(0, eval_data.pr_end, eval_data.step):
-        inter = eval_data.augmentation(slice(start, start + eval_data.step)).to(dev)
-        uids = inter[eval_data.uid_field]
-        n = uids.numel()
-        if n == 0:
-            continue
-        mn, mx = int(uids.min()), int(uids.max())
-        if mn < 0 or mx >= sampler.n_users:
-            raise ValueError(f'user_id [{mn if mn < 0 else mx}] not exist.')
-        idx = (sampler._pr_dev + torch.arange(n * m, device=dev)) % L
-        neg = sampler._rl_dev[idx].to(torch.int64)
-        sampler._pr_dev.copy_((sampler._pr_dev + n * m) % L)
-        S = model.fused_query_vectors(inter).detach().contiguous()
-        pos = inter[eval_data.iid_field].to(torch.int64).contiguous()
-        rank = torch.empty(n, dtype=torch.int32, device=dev)
-        rc = lib().mirec_rank_of_pos_f32(ptr(S), ptr(EI), EI.shape[0], EI.shape[1], ptr(pos),
-                                         ptr(neg), n, m, ptr(rank), stream_handle())
-        check(rc, 'mirec_rank_of_pos_f32')
-        ranks.append(rank)
-    rank = torch.cat(ranks) if ranks else torch.zeros(0, dtype=torch.int32, device=dev)
-    pos_idx = (rank.unsqueeze(1) == torch.arange(K, device=dev).unsqueeze(0)).cpu().numpy()
-    return topk_evaluator.evaluate_pos_idx(pos_idx, eval_data.get_pos_len_list())
-
-
-def fused_general_sampled_eval(model, eval_data, evaluator):
-    """Trainer.evaluate for a GeneralNegSampleDataLoader in evaluation (uni-N /
-    pop-N, point-wise, one batch = whole users: this fork's uni1000 validation,
-    data/utils.py:86-88) with every batch built on the device.
-
-    The reference builds each batch on the host (general_dataloader.py:210-221):
-    per user, slice its rows, sample_by_user_ids(uids, N) (one sampler call per
-    user), repeat them 1+N times with the negatives written after the positives
-    (_neg_sample_by_point_wise_sampling, :243-251), join every user/item feature
-    (unused by the general models' predict), concatenate the users, then
-    predict + evaluator.collect (trainer.py:384-409). Here one K4 launch walks the
-    batch's per-user calls in order (mirec_sample_walk_segments: the same walk,
-    the same values, the pointer advanced exactly as the calls would), the
-    [pos | negs] layout is assembled with two device scatters, and the model's
-    own predict and the evaluator's collect run on the same layout — so the
-    collected matrices are the ones the reference sequence produces on this
-    device, without the per-user host loop and the feature joins."""
-    sampler = eval_data.sampler
-    dev = model.fused_item_table().device
-    sampler.to_device(dev)
-    ds = eval_data.dataset
-    uid_f, iid_f = eval_data.uid_field, eval_data.iid_field
-    items_all = ds.inter_feat[iid_f].to(dev)
-    N = int(eval_data.neg_sample_by)
-    times = eval_data.times
-    test_bs = eval_data.config['eval_batch_size']
-    out = []
-    for start in range(0, eval_data.pr_end, eval_data.step):
-        ul = eval_data.uid_list[start:start + eval_data.step]
-        n_u = eval_data.uid2items_num[ul].astype(np.int64)
-        s_u = eval_data.uid2start[ul].astype(np.int64)
-        P = int(n_u.sum())
-        if P == 0:
-            continue
-        seg = np.r_[0, np.cumsum(n_u)]
-        # positive rows of the batch's users, user after user (dataset sorted by user)
-        rows = np.repeat(s_u - seg[:-1], n_u) + np.arange(P)
-        keys = torch.as_tensor(np.repeat(ul, n_u), dtype=torch.int64).to(dev)
-        negs = sampler.launch_segments(keys, torch.as_tensor(seg).to(dev), int(n_u.max()), N)
-        # block of user b: [its n_b positives | its n_b * N negatives], blocks in order
-        blk = np.repeat(seg[:-1] * times, n_u)                  # block start per positive
-        within = np.arange(P) - np.repeat(seg[:-1], n_u)        # positive's index in its block
-        pos_at = torch.as_tensor(blk + within).to(dev)
-        neg_blk = np.repeat(seg[:-1] * times + n_u, n_u * N)    # negatives' region start
-        neg_at = torch.as_tensor(neg_blk + np.arange(P * N) - np.repeat(seg[:-1] * N, n_u * N))
-        items = torch.empty(P * times, dtype=torch.int64, device=dev)
-        items[pos_at] = items_all[torch.as_tensor(rows).to(dev)]
-        items[neg_at.to(dev)] = negs
-        users = torch.as_tensor(np.repeat(ul, n_u * times), dtype=torch.int64).to(dev)
-        from recbole_amd.data.interaction import Interaction
-        inter = Interaction({uid_f: users, iid_f: items})
-        inter.set_additional_info(list(n_u), list(n_u * times))
-        bs = inter.length
-        if bs <= test_bs:
-            scores = model.predict(inter)
-        else:                                   # trainer.py _spilt_predict
-            scores = torch.cat([model.predict(Interaction({uid_f: users[i:i + test_bs],
-                                                           iid_f: items[i:i + test_bs]}))
-                                for i in range(0, bs, test_bs)])
-        out.append(evaluator.collect(inter, scores))
-    sampler.check_status()
-    return evaluator.evaluate(out, eval_data)
+from recbole_amd.trainer.fused_eval import (fused_full_sort_eval,  # noqa: E402,F401
+                                            fused_general_sampled_eval,
+                                            fused_seq_full_sort_eval, fused_seq_sampled_eval)
+from recbole_amd.trainer.sharded import ShardedBPRTrainStep  # noqa: E402,F401

@@ -34,10 +34,10 @@ from recbole_amd.data.dataloader.general_dataloader import GeneralNegSampleDataL
 from recbole_amd.evaluator import ProxyEvaluator
 from recbole_amd.data.dataloader.sequential_dataloader import SequentialNegSampleDataLoader
 from recbole_amd.sampler import RepeatableSampler
-from recbole_amd.trainer.fused import (FusedBPRTrainStep, ShardedBPRTrainStep,
-                                       fused_full_sort_eval,
-                                       fused_general_sampled_eval, fused_seq_full_sort_eval,
-                                       fused_seq_sampled_eval)
+from recbole_amd.trainer.fused import FusedBPRTrainStep
+from recbole_amd.trainer.fused_eval import (fused_full_sort_eval, fused_general_sampled_eval,
+                                            fused_seq_full_sort_eval, fused_seq_sampled_eval)
+from recbole_amd.trainer.sharded import ShardedBPRTrainStep
 from recbole_amd.trainer.dist import DataParallelStep, active_group
 from recbole_amd.trainer.optim import FusedAdam
 from recbole_amd.utils import (DataLoaderType, InputType, calculate_valid_score, dict2str,

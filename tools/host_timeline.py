@@ -22,7 +22,6 @@ def main():
     ap.add_argument('--reps', type=int, default=3)
     args = ap.parse_args()
     import bench
-    from recbole_amd.trainer import fused as F
     dev = torch.device('cuda', 0)
     torch.cuda.set_device(dev)
     _, _, _, _, _, step = bench.build_workload(dev, source='memory')
@@ -83,7 +82,6 @@ def main():
         for n, t in marks:
             print(f'   {t:9.1f}  {n}')
         step.end_epoch(W + K)
-    del F
 
 
 if __name__ == '__main__':

@@ -35,7 +35,7 @@ g.replay()
 torch.cuda.synchronize()
 say(f'replayed all_to_all {y.tolist()}')
 from test_gpu_e2e import _pipeline
-from recbole_amd.trainer.fused import ShardedBPRTrainStep
+from recbole_amd.trainer.sharded import ShardedBPRTrainStep
 from recbole_amd.trainer.optim import FusedAdam
 tmp = tempfile.mkdtemp()
 for graph in (False, True):

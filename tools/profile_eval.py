@@ -14,7 +14,7 @@ def main():
     import bench
     from recbole_amd import ops
     from recbole_amd.evaluator import TopKEvaluator
-    from recbole_amd.trainer.fused import fused_full_sort_eval
+    from recbole_amd.trainer.fused_eval import fused_full_sort_eval
     dev = torch.device('cuda', 0)
     config, train, test, model, opt, step = bench.build_workload(dev)
     ev = TopKEvaluator(config, ['recall', 'mrr', 'ndcg', 'hit', 'precision'])
