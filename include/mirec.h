@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define MIREC_ABI_VERSION 18
+#define MIREC_ABI_VERSION 19
 
 int mirec_abi_version(void);
 const char* mirec_last_error(void);
@@ -554,6 +554,33 @@ int mirec_adam_flush_rows_f32(const mirec_adam_table* tables, int32_t n_tables, 
                               const int32_t* rows_per_wave, const float* step_consts_dev,
                               const int32_t* step_base_dev, int32_t step_off, double beta1,
                               double beta2, double eps, double weight_decay, void* stream);
+/* The same flush restricted per table to a set of rows, so that two launches can share
+ * one flush (each row is completed by exactly one of them, with the same per-row
+ * instruction sequence as mirec_adam_flush_f32: a masked flush with want = 1 and one
+ * with want = 0, in either order or concurrently, leave p, p_alt, m, v and last as one
+ * unmasked flush does). Per table q (HOST arrays of n_tables): masks[q] = a device
+ * bitmap of ceil(n_rows / 32) uint32 words, bit r & 31 of word r >> 5 = row r, or NULL
+ * (masks itself may be NULL); row r takes part iff masks[q] == NULL or its bit ==
+ * want[q] (0 or 1); want[q] < 0 leaves table q out. A row outside the selection is
+ * neither read nor written (not even its `last`). Two dispatch forms:
+ *   scan (walk_waves == 0, rows_per_wave != NULL): mirec_adam_flush_rows_f32's grid,
+ *        the mask test added to each wave's row vote;
+ *   walk (walk_waves in [1, 65536], rows_per_wave == NULL): walk_waves one-wave
+ *        workgroups, each taking 32-row groups (one bitmap word) of every table with a
+ *        grid stride. No workgroup waits for another, so the launch can run beside
+ *        other kernels on any number of free wave slots (1,024 = one wave per SIMD).
+ * d >= 64. The target step is step_base_dev[0] + step_off. */
+int mirec_adam_flush_masked_f32(const mirec_adam_table* tables, int32_t n_tables, int32_t d,
+                                const uint32_t* const* masks, const int32_t* want,
+                                const int32_t* rows_per_wave, int32_t walk_waves,
+                                const float* step_consts_dev, const int32_t* step_base_dev,
+                                int32_t step_off, double beta1, double beta2, double eps,
+                                double weight_decay, void* stream);
+/* bitmap (ceil(n_rows / 32) uint32 words, stream-ordered: zeroed, then filled) gets bit
+ * clamp(keys[i], 0, n_rows - 1) set for every i < n_keys (ids clamped as the K35 records
+ * clamp them): the rows a chunk's steps touch, for mirec_adam_flush_masked_f32. */
+int mirec_row_bitmap(const int64_t* keys, int64_t n_keys, int64_t n_rows, uint32_t* bitmap,
+                     void* stream);
 /* K35 — one training step of the fused BPR path in ONE launch: BPR forward + backward
  * (mirec_bpr_fwd_bwd_f32's arithmetic) and the deferred Adam step
  * (mirec_adam_deferred_f32's arithmetic) of every touched row, and the look-ahead

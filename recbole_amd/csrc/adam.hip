@@ -11,6 +11,16 @@
 //    a flush replays every row up to the global step count. Same FLOPs, same
 //    bits, but each step only moves the rows it touches.
 //
+// Flush forms of d >= 64, all running the same per-row body (flush_row): one wave per
+// row (adam_flush_row_kernel), R rows per wave (adam_flush_scan_kernel), and the masked
+// flush (mirec_adam_flush_masked_f32): per table a row bitmap and the bit value that
+// selects a row, as the scan form or as a walk over a bounded grid of one-wave
+// workgroups (adam_flush_walk_kernel). A flush split by a bitmap into two launches —
+// in either order, or side by side: they share no row — leaves the same bits as one
+// flush. The train step flushes the user rows a chunk never reads with the walk form
+// beside the chunk's steps, and the rest in the chunk's closing scan-form flush
+// (trainer/fused.py BG_FLUSH).
+//
 // Restates optim.Adam.step as the reference runs it (trainer.py:109-130, 173;
 // torch optim/adam.py _single_tensor_adam, CPU, foreach=False) on
 // nn.Embedding(sparse=False) weights: every row moves every step (rows with a
@@ -252,22 +262,20 @@ template <> struct FlushVec<256> { using T = float4; };
 #endif
 constexpr int kFlushRowThreads = MIREC_FLUSH_THREADS;
 
+// One row of a flush, by one wave (lane = its D/64 columns): the body every flush form
+// of d >= 64 runs, so a row gets the same instruction sequence whichever form reaches it.
+// raw = last[r] (wave-uniform). A row that lags is read from its state's parity buffer
+// (p_alt, mirec_bpr_adam_step_f32: state t in t & 1 ? p_alt : p), replayed to `target`,
+// and completed into its target buffer AND into p (the parameter); a row that is current
+// but held in p_alt only (an odd target) is published to p; a zero-state row is left.
 template <int D>
-__global__ __launch_bounds__(kFlushRowThreads) void adam_flush_row_kernel(
-    const AdamTables tabs, const float* __restrict__ consts, const int32_t* __restrict__ step_base,
-    int step_off, AdamConsts k) {
+__device__ __forceinline__ void flush_row(const mirec_adam_table& T, int64_t r, int raw,
+                                          int target, int lane,
+                                          const float* __restrict__ consts,
+                                          const AdamConsts& k) {
   using V = typename FlushVec<D>::T;
-  constexpr int RPB = kFlushRowThreads / 64;        // rows (waves) per block
-  const int si = segment_of(tabs, blockIdx.x);
-  const mirec_adam_table& T = tabs.t[si];
-  const int64_t r = ((int64_t)blockIdx.x - tabs.block_start[si]) * RPB + (threadIdx.x >> 6);
-  if (r >= T.n_rows) return;
-  const int target = step_base[0] + step_off;
-  const int raw = __builtin_amdgcn_readfirstlane(T.last[r]);
   const int last = min(raw, target);
-  const int64_t off = r * 64 + (threadIdx.x & 63);
-  // parity buffers (p_alt, mirec_bpr_adam_step_f32): state t in t & 1 ? p_alt : p; the
-  // flush completes every row into its target buffer AND into p (the parameter)
+  const int64_t off = r * 64 + lane;
   const bool par = T.p_alt != nullptr;
   const bool odd = par && (target & 1);
   if (last >= target) {
@@ -284,7 +292,27 @@ __global__ __launch_bounds__(kFlushRowThreads) void adam_flush_row_kernel(
   reinterpret_cast<V*>(T.p)[off] = p;
   reinterpret_cast<V*>(T.m)[off] = m;
   reinterpret_cast<V*>(T.v)[off] = v;
-  if ((threadIdx.x & 63) == 0) T.last[r] = target;
+  if (lane == 0) T.last[r] = target;
+}
+
+// does row `raw` need the flush to `target`: it lags, or (an odd target with parity
+// buffers) it is current in p_alt only
+__device__ __forceinline__ bool flush_needs(const mirec_adam_table& T, int raw, int target) {
+  return min(raw, target) < target || (T.p_alt != nullptr && (target & 1) && raw != kZeroState);
+}
+
+template <int D>
+__global__ __launch_bounds__(kFlushRowThreads) void adam_flush_row_kernel(
+    const AdamTables tabs, const float* __restrict__ consts, const int32_t* __restrict__ step_base,
+    int step_off, AdamConsts k) {
+  constexpr int RPB = kFlushRowThreads / 64;        // rows (waves) per block
+  const int si = segment_of(tabs, blockIdx.x);
+  const mirec_adam_table& T = tabs.t[si];
+  const int64_t r = ((int64_t)blockIdx.x - tabs.block_start[si]) * RPB + (threadIdx.x >> 6);
+  if (r >= T.n_rows) return;
+  const int target = step_base[0] + step_off;
+  const int raw = __builtin_amdgcn_readfirstlane(T.last[r]);
+  flush_row<D>(T, r, raw, target, threadIdx.x & 63, consts, k);
 }
 
 // Flush for sparse activity (the first steps of an epoch: most rows are in the zero
@@ -295,15 +323,28 @@ __global__ __launch_bounds__(kFlushRowThreads) void adam_flush_row_kernel(
 // lists the rows that lag (or, at an odd target, are current in p_alt only), and the
 // wave completes them one after another with the one-row-per-wave body above (same
 // replay engine, same results). Blocks of four waves: R = 8 makes the grid 32x smaller.
+//
+// MASKED (mirec_adam_flush_masked_f32, the foreground form): a table with a row bitmap
+// (uint32 words, bit r = row r) takes only the rows whose bit equals `want`; the test is
+// part of `need`, and a row outside the selection is neither loaded (not even its
+// `last`: another launch may be completing it) nor marked.
 struct FlushRows {
   int32_t r[kMaxTables];
 };
+struct FlushMasks {
+  const uint32_t* bits[kMaxTables];   // per table: the row bitmap, or nullptr = every row
+  int32_t want[kMaxTables];           // the bit value that selects a row
+};
 
-template <int D>
+__device__ __forceinline__ bool mask_selects(const uint32_t* __restrict__ bits, int want,
+                                             int64_t r) {
+  return !bits || (int)((bits[r >> 5] >> (r & 31)) & 1u) == want;
+}
+
+template <int D, bool MASKED>
 __global__ __launch_bounds__(kAdamThreads) void adam_flush_scan_kernel(
     const AdamTables tabs, const float* __restrict__ consts, const int32_t* __restrict__ step_base,
-    int step_off, AdamConsts k, FlushRows rows_per_wave) {
-  using V = typename FlushVec<D>::T;
+    int step_off, AdamConsts k, FlushRows rows_per_wave, FlushMasks masks) {
   const int si = segment_of(tabs, blockIdx.x);
   const mirec_adam_table& T = tabs.t[si];
   const int R = rows_per_wave.r[si];
@@ -312,33 +353,50 @@ __global__ __launch_bounds__(kAdamThreads) void adam_flush_scan_kernel(
       (((int64_t)blockIdx.x - tabs.block_start[si]) * (kAdamThreads / 64) + (threadIdx.x >> 6)) * R;
   if (r0 >= T.n_rows) return;                          // wave-uniform
   const int target = step_base[0] + step_off;
-  const bool par = T.p_alt != nullptr;
-  const bool odd = par && (target & 1);
   int raw = kZeroState;
-  if (lane < R && r0 + lane < T.n_rows) raw = T.last[r0 + lane];
-  const bool need = min(raw, target) < target || (odd && raw != kZeroState);
-  uint64_t todo = __ballot(need);
+  if (lane < R && r0 + lane < T.n_rows &&
+      (!MASKED || mask_selects(masks.bits[si], masks.want[si], r0 + lane)))
+    raw = T.last[r0 + lane];
+  uint64_t todo = __ballot(flush_needs(T, raw, target));
   while (todo) {                                       // wave-uniform loop over its rows
     const int i = __builtin_ctzll(todo);
     todo &= todo - 1;
-    const int64_t r = r0 + i;
-    const int rraw = __shfl(raw, i, 64);
-    const int last = min(rraw, target);
-    const int64_t off = r * 64 + lane;
-    if (last >= target) {                              // current, in p_alt only: publish
-      reinterpret_cast<V*>(T.p)[off] = reinterpret_cast<const V*>(T.p_alt)[off];
-      continue;
+    flush_row<D>(T, r0 + i, __shfl(raw, i, 64), target, lane, consts, k);
+  }
+}
+
+// The masked flush's background form: a bounded grid of one-wave workgroups, made to run
+// beside other kernels. Wave w takes the row groups w, w + waves, ... of each table in
+// turn (kWalkRows consecutive rows: one bitmap word, a wave-uniform load), lists the
+// selected rows that need the flush with one ballot and completes them one after another
+// with the body above. No workgroup waits for another (no counter, no barrier): the
+// launch ends whatever else runs, and with any grid. Default wave priority.
+constexpr int kWalkRows = 32;
+
+template <int D>
+__global__ __launch_bounds__(64) void adam_flush_walk_kernel(
+    const AdamTables tabs, const float* __restrict__ consts, const int32_t* __restrict__ step_base,
+    int step_off, AdamConsts k, FlushMasks masks) {
+  const int lane = threadIdx.x;
+  const int target = step_base[0] + step_off;
+  for (int si = 0; si < tabs.n_seg; ++si) {
+    const mirec_adam_table& T = tabs.t[si];
+    const uint32_t* __restrict__ bits = masks.bits[si];
+    const uint32_t flip = masks.want[si] ? 0u : ~0u;
+    const int64_t groups = (T.n_rows + kWalkRows - 1) / kWalkRows;
+    for (int64_t g = blockIdx.x; g < groups; g += gridDim.x) {   // wave-uniform
+      const int64_t r0 = g * kWalkRows;
+      const uint32_t sel = bits ? (bits[g] ^ flip) : ~0u;
+      int raw = kZeroState;
+      if (lane < kWalkRows && r0 + lane < T.n_rows && ((sel >> lane) & 1u))
+        raw = T.last[r0 + lane];
+      uint64_t todo = __ballot(flush_needs(T, raw, target));
+      while (todo) {
+        const int i = __builtin_ctzll(todo);
+        todo &= todo - 1;
+        flush_row<D>(T, r0 + i, __shfl(raw, i, 64), target, lane, consts, k);
+      }
     }
-    V p = reinterpret_cast<const V*>((par && (last & 1)) ? T.p_alt : T.p)[off];
-    V m = reinterpret_cast<const V*>(T.m)[off];
-    V v = reinterpret_cast<const V*>(T.v)[off];
-    replay<V, true>(p, m, v, last, target, consts, k);
-    MIREC_WORK(10, 1);
-    if (odd) reinterpret_cast<V*>(T.p_alt)[off] = p;
-    reinterpret_cast<V*>(T.p)[off] = p;
-    reinterpret_cast<V*>(T.m)[off] = m;
-    reinterpret_cast<V*>(T.v)[off] = v;
-    if (lane == 0) T.last[r] = target;
   }
 }
 
@@ -354,7 +412,8 @@ int launch_adam(Sched sched, const mirec_adam_table* tables, int32_t n_tables,
                 const int64_t* n_max_uniq, int32_t d, const float* consts,
                 const int32_t* step_base, int32_t step_off, double beta1, double beta2,
                 double eps, double weight_decay, void* stream, const char* what,
-                const int32_t* flush_rows = nullptr) {
+                const int32_t* flush_rows = nullptr, const FlushMasks* masks = nullptr,
+                int walk_waves = 0) {
   if (n_tables < 1 || n_tables > kMaxTables || !tables || !consts || !step_base) {
     set_error("%s: bad arguments (n_tables=%d)", what, n_tables);
     return -1;
@@ -397,6 +456,16 @@ int launch_adam(Sched sched, const mirec_adam_table* tables, int32_t n_tables,
     }
     scan = true;
   }
+  // masked flush (mirec_adam_flush_masked_f32): the scan form with the row bitmaps, or
+  // the walk form on a grid of walk_waves one-wave workgroups
+  const bool walk = masks && walk_waves > 0;
+  if (masks && (sched != Sched::kFlush || d < 64 || (!scan && !walk))) {
+    set_error("%s: a masked flush needs d >= 64 and rows per wave or a wave count", what);
+    return -1;
+  }
+  FlushMasks fm;
+  memset(&fm, 0, sizeof(fm));
+  if (masks) fm = *masks;
   AdamTables tabs;
   memset(&tabs, 0, sizeof(tabs));
   const bool deferred = sched == Sched::kDeferred;
@@ -435,7 +504,10 @@ int launch_adam(Sched sched, const mirec_adam_table* tables, int32_t n_tables,
       return -1;
     }
     tabs.t[q] = t;
-    if (deferred) {
+    if (walk) {
+      tabs.block_start[q] = 0;                 // every wave walks every table
+      if (t.n_rows > 0) blocks = walk_waves;
+    } else if (deferred) {
       const int rpb = (pair && q == 1) ? deferred_block(1) : deferred_block(d / dvec) / (d / dvec);
       const int64_t nb = (n_max_uniq[q] + rpb - 1) / rpb;
       tabs.block_start[2 * q] = blocks;
@@ -481,9 +553,15 @@ int launch_adam(Sched sched, const mirec_adam_table* tables, int32_t n_tables,
                                       : adam_deferred_kernel<DD, float>),                    \
                          grd, dim3(deferred_block(DD / dvec)), 0, st, tabs, consts,          \
                          step_base, step_off, k);                                            \
+    else if (DD >= 64 && walk)                                                               \
+      hipLaunchKernelGGL(adam_flush_walk_kernel<(DD >= 64 ? DD : 64)>, grd, dim3(64), 0, st,   \
+                         tabs, consts, step_base, step_off, k, fm);                          \
+    else if (DD >= 64 && scan && masks)                                                      \
+      hipLaunchKernelGGL((adam_flush_scan_kernel<(DD >= 64 ? DD : 64), true>), grd, blk, 0,    \
+                         st, tabs, consts, step_base, step_off, k, fr, fm);                  \
     else if (DD >= 64 && scan)                                                               \
-      hipLaunchKernelGGL(adam_flush_scan_kernel<(DD >= 64 ? DD : 64)>, grd, blk, 0, st, tabs,  \
-                         consts, step_base, step_off, k, fr);                                \
+      hipLaunchKernelGGL((adam_flush_scan_kernel<(DD >= 64 ? DD : 64), false>), grd, blk, 0,   \
+                         st, tabs, consts, step_base, step_off, k, fr, fm);                  \
     else if (DD >= 64)                                                                       \
       hipLaunchKernelGGL(adam_flush_row_kernel<(DD >= 64 ? DD : 64)>, grd,                   \
                          dim3(kFlushRowThreads), 0, st, tabs,                                \
@@ -579,6 +657,44 @@ extern "C" int mirec_adam_flush_rows_f32(const mirec_adam_table* tables, int32_t
   return launch_adam(Sched::kFlush, tables, n_tables, nullptr, d, step_consts_dev,
                      step_base_dev, step_off, beta1, beta2, eps, weight_decay, stream,
                      "mirec_adam_flush_rows_f32", rows_per_wave);
+}
+
+extern "C" int mirec_adam_flush_masked_f32(const mirec_adam_table* tables, int32_t n_tables,
+                                           int32_t d, const uint32_t* const* masks,
+                                           const int32_t* want, const int32_t* rows_per_wave,
+                                           int32_t walk_waves, const float* step_consts_dev,
+                                           const int32_t* step_base_dev, int32_t step_off,
+                                           double beta1, double beta2, double eps,
+                                           double weight_decay, void* stream) {
+  const char* what = "mirec_adam_flush_masked_f32";
+  if (!tables || n_tables < 1 || n_tables > kMaxTables || !want || walk_waves < 0 ||
+      walk_waves > 65536 || (walk_waves == 0) != (rows_per_wave != nullptr)) {
+    set_error("%s: bad arguments (rows per wave for the scan form, or a wave count in "
+              "[1, 65536] for the walk form)", what);
+    return -1;
+  }
+  // the tables that take part (want < 0: left out), in order
+  mirec_adam_table sel[kMaxTables];
+  int32_t rows[kMaxTables];
+  FlushMasks fm;
+  memset(&fm, 0, sizeof(fm));
+  int n = 0;
+  for (int q = 0; q < n_tables; ++q) {
+    if (want[q] < 0) continue;
+    if (want[q] > 1) {
+      set_error("%s: want[%d] = %d not in {-1, 0, 1}", what, q, want[q]);
+      return -1;
+    }
+    sel[n] = tables[q];
+    rows[n] = rows_per_wave ? rows_per_wave[q] : 1;
+    fm.bits[n] = masks ? masks[q] : nullptr;
+    fm.want[n] = want[q];
+    ++n;
+  }
+  if (n == 0) return 0;
+  return launch_adam(Sched::kFlush, sel, n, nullptr, d, step_consts_dev, step_base_dev, step_off,
+                     beta1, beta2, eps, weight_decay, stream, what,
+                     rows_per_wave ? rows : nullptr, &fm, walk_waves);
 }
 
 extern "C" int mirec_adam_sparse_grad_f32(float* p, float* m, float* v, int64_t n_rows,

@@ -509,6 +509,9 @@ constexpr int kSumLoads = MIREC_STEP_SUM_LOADS;
 #ifndef MIREC_STEP_WAVES
 #define MIREC_STEP_WAVES 5               // waves per SIMD the register budget allows (6: 80
 #endif                                   // VGPRs, 28 B/lane spilled; 5: 86, no spill)
+#ifndef MIREC_STEP_PRIO
+#define MIREC_STEP_PRIO 3                // wave priority of the step's waves (0..3)
+#endif
 
 template <int D>
 __global__ __launch_bounds__(D / Lanes<typename StepVec<D>::T>::n * StepRows<D>::n,
@@ -524,6 +527,10 @@ void bpr_adam_step_kernel(
   static_assert(RPB == 1 || TPB == 64, "several rows per workgroup need one wave per row");
   constexpr int LPR = D / 4;               // lanes per contribution (float4 each, K3's layout)
   constexpr int NG = TPB / LPR;            // contributions in flight per row
+  // The step is a chain of dependent loads with short bursts of arithmetic: its waves go
+  // ahead of default-priority waves that share their SIMD (the masked flush's walk form,
+  // adam.hip, runs beside a chunk's steps). Issue order only: no result depends on it.
+  __builtin_amdgcn_s_setprio(MIREC_STEP_PRIO);
   __shared__ float cont_all[RPB][NG][D];
   __shared__ int s_last_all[RPB];
   // the row of this wave: wave-uniform, so the row's indices stay in scalar registers
@@ -825,6 +832,35 @@ extern "C" int mirec_step_records(const int64_t* user_keys, const int64_t* item_
 }
 
 extern "C" int64_t mirec_step_record_ints(int64_t per) { return per < 0 ? -1 : rec_ints(per); }
+
+namespace mirec {
+// bit clamp(keys[i]) of the bitmap set for every key (clamp_id: as the records clamp)
+__global__ __launch_bounds__(256) void row_bitmap_kernel(const int64_t* __restrict__ keys,
+                                                         int64_t n_keys, int64_t n_rows,
+                                                         uint32_t* __restrict__ bitmap) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_keys) return;
+  const int64_t r = clamp_id(keys[i], n_rows);
+  atomicOr(bitmap + (r >> 5), 1u << (r & 31));
+}
+}  // namespace mirec
+
+extern "C" int mirec_row_bitmap(const int64_t* keys, int64_t n_keys, int64_t n_rows,
+                                uint32_t* bitmap, void* stream) {
+  const char* what = "mirec_row_bitmap";
+  if (n_keys < 0 || n_rows <= 0 || !bitmap || (n_keys > 0 && !keys) ||
+      n_keys > (int64_t)INT32_MAX * 256) {
+    set_error("%s: bad arguments", what);
+    return -1;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int rc = hip_status(hipMemsetAsync(bitmap, 0, (size_t)((n_rows + 31) / 32) * 4, st), what);
+  if (rc) return rc;
+  if (n_keys == 0) return 0;
+  hipLaunchKernelGGL(row_bitmap_kernel, dim3((unsigned)((n_keys + 255) / 256)), dim3(256), 0, st,
+                     keys, n_keys, n_rows, bitmap);
+  return launch_status(what);
+}
 
 #if defined(MIREC_STEP_COUNT)
 // diagnostic build only: copy (and clear) this unit's executed-work counters (16 x u64)

@@ -77,6 +77,43 @@ def chunk_flags(plan, Bg, flush_every, flush_at, times, adam_mode, d, n_rows, bu
     return flags
 
 
+def bg_flush_chunks(plan, flags, Bg, adam_mode, fused_step, use_graph, min_steps=1,
+                    enabled=True):
+    """Per chunk of `plan`: does its flush split into a background part (the user rows
+    the chunk never reads, flushed early beside the chunk's steps) and a masked
+    foreground part (fused.py)? Only for a chunk of full batches that ends with a flush
+    on the one-GPU fused step (K35: `fused_step`) with the deferred schedule and captured
+    chunk graphs; never on the streamed, replicated or sharded steps (their fused_step
+    is False). The background part runs on a bounded grid, several times slower than
+    the full flush it replaces, so it pays only where the chunk's own steps cover it:
+    the chunk has at least min_steps steps, and the lag it flushes is no longer than the
+    chunk (the chunk before it flushed: no entry catch-up). Whether such a chunk then
+    runs as a whole graph is decided when it runs (bg_flush_now)."""
+    on = bool(enabled and fused_step and use_graph and adam_mode == 'deferred')
+    return [bool(on and flush and not entry and Bc == Bg and nb >= min_steps)
+            for (_, nb, Bc), (entry, flush) in zip(plan, flags)]
+
+
+def bg_flush_now(planned, c0, c1, nb, graph_ready, timed_kernels):
+    """Does the run of batches [c0, c1) of an nb-batch chunk launch the background flush:
+    the chunk was planned for it (bg_flush_chunks) and replays its captured graph as a
+    whole. A chunk entered mid-way, cut short, timed per kernel or without a captured
+    graph runs eagerly and keeps the full flush."""
+    return bool(planned and c0 == 0 and c1 == nb and graph_ready and not timed_kernels)
+
+
+def masked_flush_rows(flush, nb, Bg, n_users, max_rows):
+    """Rows per wave of a chunk's masked foreground flush, from its full flush's `flush`
+    (flush_rows): the user table takes only the rows the chunk's nb batches read, at
+    most nb * Bg of its n_users rows, so R = the largest power of two <= max_rows with
+    R x min(1, nb * Bg / n_users) <= 1; the item table is flushed whole, as before."""
+    frac = min(1.0, nb * Bg / max(n_users, 1))
+    r = 1
+    while r * 2 <= max_rows and r * 2 * frac <= 1.0:
+        r *= 2
+    return (r,) + tuple(flush[1:])
+
+
 def chunk_of(plan, b):
     """Index of the chunk of `plan` holding global batch b (0 below the first)."""
     return max(bisect.bisect_right(plan, (b, math.inf)) - 1, 0)

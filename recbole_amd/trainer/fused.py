@@ -16,6 +16,11 @@ model side (main stream, per batch)
                                            or 'streamed', bit-identical (see adam.hip)
   chunk_finish                            per-step mean losses kept on the device
   K5 flush         ('deferred' only)      once per chunk: every row caught up
+background stream (one GPU, K35; BG_FLUSH)
+  K5 masked flush  (walk form)            beside a flushing chunk's steps: the user rows the
+                                           chunk never reads, to the chunk's end step; the
+                                           chunk's own flush then takes only the user rows
+                                           it read, and the item table
 
 The batch is a contiguous slice of the train table resident in HBM, shuffled
 once per epoch with torch.randperm on the CPU generator (interaction.py:272-276)
@@ -36,6 +41,15 @@ row is next touched (or at the per-chunk flush), with the same per-element
 arithmetic, so the parameters after a flush are bit-identical to the streamed
 schedule's while a step moves only the rows its batch touches. Parameters are
 complete after end_epoch() / sync_params().
+
+Background flush: the rows a chunk's closing flush works longest on are the user rows
+that sat idle for the whole chunk. Nothing reads them before the chunk ends and their
+step constants are staged for the epoch, so they are flushed early, on a third side
+stream, while the chunk's K35 launches (latency-bound, at a raised wave priority) leave
+most of the VALU idle: row sets are disjoint (a bitmap of the chunk's user keys, built
+with its grouping), every row gets the same arithmetic from exactly one launch, and the
+model side waits for the background's event before the next chunk or any read of the
+parameters. Which chunks get one is chunk_plan.bg_flush_chunks.
 
 The chunk plan (sizes, ramp, entry / flush flags) is trainer/chunk_plan.py; the
 row-sharded step is trainer/sharded.py and the evaluations are trainer/fused_eval.py
@@ -143,6 +157,9 @@ class _Slot(object):
         # per table (users, items): the grouping of each batch's keys
         self.tab = tab or [_Lists(C, per, dev, ahead) for per in (Bg, KI)]
         self.records = None          # K35 row / contribution records (FusedBPRTrainStep)
+        self.bitmap = None           # user rows the chunk reads, one bit per row (BG_FLUSH)
+        self.bg_done = None          # event after the chunk's background flush
+        self.bg_busy = False         # a background flush was issued since the last refill
         self.prep = None             # mirec_chunk_prep descriptor (_chunk_prep)
         self.ready, self.walked, self.free = (torch.cuda.Event() for _ in range(3))
         # torch creates an event's HIP object at its first record (hipEventCreate, tens of
@@ -154,7 +171,8 @@ class _Slot(object):
         self.group_pending = False   # walked, grouping not yet issued
         self.ready_on_model = False  # prepared on the model's stream: no wait for `ready`
         self.chunk = None            # (first global batch, n batches, global batch size)
-        self.graphs = {}             # (n batches, entry, flush) -> HIP graph of the model side
+        # (n batches, entry, flush, masked) -> HIP graph of the model side
+        self.graphs = {}
 
 
 class FusedBPRTrainStep(object):
@@ -211,8 +229,26 @@ class FusedBPRTrainStep(object):
     # K4s (mirec_sample_walk_spec): the chunk's walk by speculation (exact; two launches
     # per 16 batches instead of a serial walk of ~10 us per batch)
     SPEC_WALK = os.environ.get('MIREC_SPEC_WALK', '1') != '0'
-    # (RAMP, FLUSH_EVERY, FLUSH_SPARSE_MAX_ROWS and MAIN_FIRST are read at begin_epoch /
-    # when a chunk is entered: an instance may set its own after construction)
+    # Background flush (one GPU, K35, deferred schedule, captured chunk graphs): the user
+    # rows a flushing chunk never reads are flushed to the chunk's end beside its steps, on
+    # a third side stream, by a bounded grid of BG_WAVES one-wave workgroups (mirec_adam_
+    # flush_masked_f32, walk form); the chunk's closing flush then takes only the user rows
+    # it did read, and the item table. Bit-identical to the full flush (each row is
+    # completed by exactly one of the two, with the same arithmetic). MIREC_BG_FLUSH=0:
+    # one full flush after the chunk's steps.
+    BG_FLUSH = os.environ.get('MIREC_BG_FLUSH', '1') != '0'
+    # waves of the background grid (1,024 = one per SIMD) and the shortest chunk that gets
+    # one. The background part is latency-bound on so few waves: it takes ~0.8 ms for 64
+    # lagging steps beside K35 where the full flush takes 0.33 ms alone, and ~0.25 ms for 8
+    # (per-row load / store round trips), so a short chunk's steps do not cover it (C2,
+    # warm-up 5 + 20 steps: 23.8 M positives/s with it against 24.7 M without). Measured on
+    # C2 (64 + 256 steps): 25.0 M at 1,024 waves, 25.9 M at 1,536, 25.5 M at 2,048, 24.6 M
+    # at 3,072 (K35 loses more than the shorter background saves); 24.4 M without.
+    BG_WAVES = int(os.environ.get('MIREC_BG_WAVES', '1536'))
+    BG_MIN_STEPS = 32
+    # (RAMP, FLUSH_EVERY, FLUSH_SPARSE_MAX_ROWS, MAIN_FIRST, BG_FLUSH, BG_WAVES and
+    # BG_MIN_STEPS are read at begin_epoch / when a chunk is entered: an instance may set
+    # its own after construction)
 
     def __init__(self, model, optimizer, train_data, chunk=None, use_graph=True,
                  adam_mode='deferred', dist=None, fused_step=None):
@@ -258,7 +294,10 @@ class FusedBPRTrainStep(object):
         # keys + K4 walk on one side stream, K2 grouping + look-ahead lists on a
         # second: chunk c+1 walks while chunk c is grouped; neither shares the main
         # stream's hardware queue (_prep_streams_for)
-        self.prep_stream, self.group_stream = _prep_streams_for(dev)
+        # and, for the one-GPU fused step, a third for the background flush (BG_FLUSH)
+        side = _prep_streams_for(dev, 3 if self.fused_step else 2)
+        self.prep_stream, self.group_stream = side[:2]
+        self.bg_stream = side[2] if self.fused_step else None
         self.zero_i32 = torch.zeros(1, dtype=torch.int32, device=dev)
         self.loss_hist = torch.zeros(1, dtype=torch.float32, device=dev)
         self.consts = torch.zeros(4, dtype=torch.float32, device=dev)
@@ -274,6 +313,10 @@ class FusedBPRTrainStep(object):
         self._users = self._items = None
         self.n_batches = 0
         self._plan, self._flags, self._flush_at = [], [], set()
+        self._bg = []               # per chunk: flush split into background + masked (BG_FLUSH)
+        self._bg_pending = None     # event of a background flush the model side has not awaited
+        self._bg_mark = torch.cuda.Event()   # model-side work a background flush follows
+        self._bg_mark.record(torch.cuda.current_stream(dev))
         self._busy0 = None          # rows outside the zero state at the epoch start
         self._batches_enqueued = 0
         self._current = True        # no step enqueued since the last flush
@@ -312,6 +355,9 @@ class FusedBPRTrainStep(object):
             for sl in self.slots:
                 sl.records = [torch.empty(self.C * w, dtype=torch.int32, device=dev)
                               for w in self._rec_ints(self.Bg)]
+                sl.bitmap = torch.zeros((self.nU + 31) // 32, dtype=torch.int32, device=dev)
+                sl.bg_done = torch.cuda.Event()
+                sl.bg_done.record(torch.cuda.current_stream(dev))
             # split rows' hand-off scratch (one launch at a time on the compute stream)
             self._step_scratch = ops.step_scratch(self.Bg, T, d, dev)
         self._n_max = (ctypes.c_int64 * 2)(self.Bg, (1 + T) * self.Bg)
@@ -341,6 +387,10 @@ class FusedBPRTrainStep(object):
         prep and group streams order their next launches after it)."""
         if slot.free_recorded and on is None and not slot.free.query():
             self.prep_stream.wait_event(slot.free)     # (a completed event needs no wait)
+        if slot.bg_busy:
+            # the slot's bitmap is read until its last chunk's background flush ends
+            (on if on is not None else self.prep_stream).wait_event(slot.bg_done)
+            slot.bg_busy = False
         if self._dp_slice(chunk[2]):
             self._prepare_dp(slot, chunk)
         else:
@@ -439,6 +489,12 @@ class FusedBPRTrainStep(object):
     def _group_on(self, slot, st):
         check(lib().mirec_prepare_chunk_group(ctypes.byref(slot.prep), st.cuda_stream),
               'mirec_prepare_chunk_group')
+        b0, nb, Bc = slot.chunk
+        if slot.bitmap is not None and self._bg[self._chunk_of(b0)]:
+            # the user rows the chunk reads (whichever path grouped it), for its masked flushes
+            check(lib().mirec_row_bitmap(slot.user_keys.data_ptr(), nb * Bc, self.nU,
+                                         slot.bitmap.data_ptr(), st.cuda_stream),
+                  'mirec_row_bitmap')
         slot.ready.record(st)
         slot.group_pending = False
 
@@ -656,6 +712,42 @@ class FusedBPRTrainStep(object):
             self._launch('flush', stream, 'mirec_adam_flush_f32', self._tables, 2, self.d,
                          *self._sched(0))
 
+    def _flush_masked(self, stream, slot, rows):
+        """The foreground half of a split flush (a chunk's last launch): the user rows in
+        the slot's bitmap and every item row, `rows` per wave (chunk_plan.masked_flush_rows),
+        to step_idx applied steps. The bitmap pointer is the slot's: graph-capturable."""
+        self._launch('flush', stream, 'mirec_adam_flush_masked_f32', self._tables, 2, self.d,
+                     (ctypes.c_void_p * 2)(slot.bitmap.data_ptr(), None),
+                     (ctypes.c_int32 * 2)(1, 1), (ctypes.c_int32 * 2)(*rows), 0,
+                     *self._sched(0))
+
+    def _flush_background(self, slot, t_end, stream):
+        """The background half, issued before the chunk's graph: the user rows NOT in the
+        slot's bitmap to t_end applied steps (epoch-relative, absolute: a device zero as
+        the base), on the background stream — after the model-side work enqueued so far
+        (earlier chunks without a flush may have touched these rows) and after the
+        bitmap. The chunk's steps, entry catch-up, look-ahead and closing flush only
+        touch user rows in the bitmap; the model side waits for the event before the next
+        chunk (run_batches) and before the parameters are read (sync_params)."""
+        bg = self.bg_stream
+        self._bg_mark.record(stream)
+        bg.wait_event(self._bg_mark)
+        bg.wait_event(slot.ready)
+        check(lib().mirec_adam_flush_masked_f32(
+            self._tables, 2, self.d, (ctypes.c_void_p * 2)(slot.bitmap.data_ptr(), None),
+            (ctypes.c_int32 * 2)(0, -1), None, int(self.BG_WAVES), self.consts.data_ptr(),
+            self.zero_i32.data_ptr(), int(t_end), *self._adam_args, bg.cuda_stream),
+            'mirec_adam_flush_masked_f32')
+        slot.bg_done.record(bg)
+        slot.bg_busy = True
+        self._bg_pending = slot.bg_done
+
+    def _await_background(self, stream):
+        """Order `stream` after an outstanding background flush."""
+        if self._bg_pending is not None:
+            stream.wait_event(self._bg_pending)
+            self._bg_pending = None
+
     def _entry_lists(self, slot):
         """(row list, device count) per table: the rows batch 0 of `slot` reads."""
         return [(l.uniq, l.nu) for l in slot.tab]
@@ -684,12 +776,13 @@ class FusedBPRTrainStep(object):
             self._gs = float(np.float32(1.0) / np.float32(R))
         return self._gs
 
-    def _graph_for(self, slot, nb, entry, flush):
+    def _graph_for(self, slot, nb, entry, flush, masked=False):
         """HIP graph of the model-side steps of an nb-batch chunk in `slot`, with
-        the entry catch-up and / or the closing flush (captured once per (slot, nb,
-        entry, flush); capture synchronizes, so begin_epoch captures every variant
-        its plan uses before any batch runs)."""
-        key = (nb, entry, flush)
+        the entry catch-up and / or the closing flush — `masked`: its foreground half
+        (_flush_masked) — captured once per (slot, nb, entry, flush, masked); capture
+        synchronizes, so begin_epoch captures every variant its plan uses before any
+        batch runs. One chain of launches: no parallel branches."""
+        key = (nb, entry, flush, masked)
         g = slot.graphs.get(key)
         if g is None:
             g = torch.cuda.CUDAGraph()
@@ -701,22 +794,25 @@ class FusedBPRTrainStep(object):
                 for c in range(nb):
                     self._step(slot, c, self.Bg, cap, c, c + 1 < nb)
                 self._finish(0, nb, self.Bg, cap)
-                if flush:
+                if flush and masked:
+                    self._flush_masked(cap, slot, chunk_plan.masked_flush_rows(
+                        flush, nb, self.Bg, self.nU, self.FLUSH_SPARSE_MAX_ROWS))
+                elif flush:
                     self._flush(cap, flush)
             torch.cuda.current_stream(self.device).wait_stream(cap)
             slot.graphs[key] = g
         return g
 
     def _capture_variants(self):
-        """Capture the model-side graph of every (slot, size, entry, flush) variant the
-        epoch's chunk plan uses."""
+        """Capture the model-side graph of every (slot, size, entry, flush, masked)
+        variant the epoch's chunk plan uses."""
         S = len(self.slots)
         # flush flags are False, True or a tuple of row counts: sort by their repr
-        variants = sorted({(k % S, n, e, f) for k, ((_, n, Bc), (e, f)) in
-                           enumerate(zip(self._plan, self._flags)) if Bc == self.Bg},
-                          key=lambda v: (v[0], v[1], v[2], repr(v[3])))
-        for k, n, e, f in variants:
-            self._graph_for(self.slots[k], n, e, f)
+        variants = sorted({(k % S, n, e, f, bg) for k, ((_, n, Bc), (e, f), bg) in
+                           enumerate(zip(self._plan, self._flags, self._bg)) if Bc == self.Bg},
+                          key=lambda v: (v[0], v[1], v[2], repr(v[3]), v[4]))
+        for k, n, e, f, bg in variants:
+            self._graph_for(self.slots[k], n, e, f, bg)
 
     # ------------------------------------------------------------------ epoch API
     def begin_epoch(self, cuts=(), hold_prep_from=None, flush_at=()):
@@ -729,6 +825,7 @@ class FusedBPRTrainStep(object):
         whose chunk (and every later one) is not prepared until release_prep() —
         so a timed region that starts there contains its own chunks' sampler walk
         and grouping."""
+        self._await_background(torch.cuda.current_stream(self.device))
         data = self.data
         if data.shuffle:
             data._shuffle()                     # randperm (CPU RNG) + device reorder
@@ -771,6 +868,9 @@ class FusedBPRTrainStep(object):
         self._flags = chunk_plan.chunk_flags(self._plan, self.Bg, self.FLUSH_EVERY,
                                              self._flush_at, self.times, self.adam_mode, self.d,
                                              n_rows, self._busy0, self.FLUSH_SPARSE_MAX_ROWS)
+        self._bg = chunk_plan.bg_flush_chunks(self._plan, self._flags, self.Bg, self.adam_mode,
+                                              self.fused_step, self.use_graph,
+                                              self.BG_MIN_STEPS, self.BG_FLUSH)
         if self.use_graph:                      # capture up front: capture synchronizes
             self._capture_variants()
         self.prep_stream.wait_stream(torch.cuda.current_stream(self.device))
@@ -868,12 +968,18 @@ class FusedBPRTrainStep(object):
             k = self._chunk_of(b)
             b0, nb, Bc = self._plan[k]
             entry, flush = self._flags[k]
+            # every row the chunk may read is complete only after the previous chunk's
+            # background flush (and its slot's next preparation follows this wait too)
+            self._await_background(stream)
             self._enter_chunk(k, stream)
             slot = self.slots[k % len(self.slots)]
             c0, c1 = b - b0, min(nb, b_end - b0)
-            key = (nb, entry, flush)
+            key = (nb, entry, flush, self._bg[k])
             if (self.use_graph and c0 == 0 and c1 == nb and Bc == self.Bg
                     and self.kernel_events is None and key in slot.graphs):
+                if chunk_plan.bg_flush_now(self._bg[k], c0, c1, nb, key in slot.graphs,
+                                           self.kernel_events is not None):
+                    self._flush_background(slot, b0 + nb, stream)
                 slot.graphs[key].replay()
                 self._current = flush
             else:
@@ -906,6 +1012,7 @@ class FusedBPRTrainStep(object):
     def sync_params(self):
         """Make the parameters current (deferred schedule: flush every row, unless
         the last enqueued work was a chunk's closing flush)."""
+        self._await_background(torch.cuda.current_stream(self.device))
         if not self._current:
             self._flush(torch.cuda.current_stream(self.device),
                         self._flush_rows(self._batches_enqueued))
@@ -916,6 +1023,7 @@ class FusedBPRTrainStep(object):
         per-batch losses back (one sync)."""
         n_done = self.n_batches if n_done is None else n_done
         stream = torch.cuda.current_stream(self.device)
+        self._await_background(stream)
         stream.wait_stream(self.prep_stream)
         stream.wait_stream(self.group_stream)
         self.sync_params()
@@ -933,6 +1041,7 @@ class FusedBPRTrainStep(object):
     def close(self):
         """Drop the captured chunk graphs (they hold collectives of the process
         group: release them before torch.distributed.destroy_process_group)."""
+        self._await_background(torch.cuda.current_stream(self.device))
         torch.cuda.synchronize(self.device)
         self._drop_graphs()
         torch.cuda.synchronize(self.device)
