@@ -581,6 +581,29 @@ int mirec_adam_flush_masked_f32(const mirec_adam_table* tables, int32_t n_tables
  * clamp them): the rows a chunk's steps touch, for mirec_adam_flush_masked_f32. */
 int mirec_row_bitmap(const int64_t* keys, int64_t n_keys, int64_t n_rows, uint32_t* bitmap,
                      void* stream);
+/* First-read table of a chunk, from one table's K2 groupings: first[r] (n_rows int32,
+ * stream-ordered: reset, then filled) = the smallest batch index c < n_batches whose
+ * distinct-row list (uniq + c * per, n_uniq[c] entries, each in [0, n_rows)) holds row r,
+ * or MIREC_FIRST_NOT_READ for a row no batch of the chunk reads. per = int32 per batch
+ * block of uniq; n_batches <= 32767. For mirec_adam_flush_first_f32. */
+#define MIREC_FIRST_NOT_READ (-1)
+int mirec_first_read(const int32_t* uniq, const int32_t* n_uniq, int64_t n_batches, int64_t per,
+                     int64_t n_rows, int32_t* first, void* stream);
+/* The flush with a target per row (the chunk advance of the fused train step): per table q
+ * (HOST arrays of n_tables) first[q] = a device array of n_rows int32 as mirec_first_read
+ * writes it, or NULL to leave table q out. Row r takes part iff first[q][r] !=
+ * MIREC_FIRST_NOT_READ, and its target is step_base_dev[0] + step_off + first[q][r]: a row
+ * whose `last` is below its target replays last..target-1 with a zero gradient, exactly as
+ * mirec_adam_flush_f32 with that target does to it (the same per-row instruction sequence:
+ * read from its state's parity buffer, completed into target & 1 ? p_alt : p and into p,
+ * last = target). Every other row — not read, in the zero state, at or past its target —
+ * is neither loaded nor written (no p_alt -> p publishing: the rows are read by parity
+ * next). The grid is mirec_adam_flush_rows_f32's (rows_per_wave per table). d >= 64. */
+int mirec_adam_flush_first_f32(const mirec_adam_table* tables, int32_t n_tables, int32_t d,
+                               const int32_t* const* first, const int32_t* rows_per_wave,
+                               const float* step_consts_dev, const int32_t* step_base_dev,
+                               int32_t step_off, double beta1, double beta2, double eps,
+                               double weight_decay, void* stream);
 /* K35 — one training step of the fused BPR path in ONE launch: BPR forward + backward
  * (mirec_bpr_fwd_bwd_f32's arithmetic) and the deferred Adam step
  * (mirec_adam_deferred_f32's arithmetic) of every touched row, and the look-ahead

@@ -212,6 +212,10 @@ SIGNATURES = {
                                             _P, c_int32, _P, _P, c_int32, c_double, c_double,
                                             c_double, c_double, _P]),
     "mirec_row_bitmap": (c_int, [_P, c_int64, c_int64, _P, _P]),
+    "mirec_first_read": (c_int, [_P, _P, c_int64, c_int64, c_int64, _P, _P]),
+    "mirec_adam_flush_first_f32": (c_int, [ctypes.POINTER(AdamTable), c_int32, c_int32, _P, _P,
+                                           _P, _P, c_int32, c_double, c_double, c_double,
+                                           c_double, _P]),
     "mirec_bpr_adam_step_f32": (c_int, [ctypes.POINTER(AdamTable), _P, c_int32, _P, c_int64,
                                         c_int32, ctypes.c_float, ctypes.c_float, _P, _P, _P,
                                         _P, _P, _P, _P, _P, _P, _P, _P, c_int32, c_double,

@@ -365,6 +365,46 @@ __global__ __launch_bounds__(kAdamThreads) void adam_flush_scan_kernel(
   }
 }
 
+// The scan form with a target per row (mirec_adam_flush_first_f32, the chunk advance):
+// first[r] = the batch of the chunk that reads row r first (mirec_first_read), so the row's
+// target is the chunk's base step + first[r]. A row takes part iff it is read at all and
+// lags its own target; every other row is neither loaded nor marked (nothing is published
+// to p here: the step kernels read these rows by parity). The rows are completed by the
+// one-row-per-wave body above, each with its own (wave-uniform) target.
+struct FlushFirst {
+  const int32_t* first[kMaxTables];   // per table: first read per row, or kFirstNotRead
+};
+constexpr int kFirstNotRead = MIREC_FIRST_NOT_READ;
+
+template <int D>
+__global__ __launch_bounds__(kAdamThreads) void adam_flush_first_kernel(
+    const AdamTables tabs, const float* __restrict__ consts, const int32_t* __restrict__ step_base,
+    int step_off, AdamConsts k, FlushRows rows_per_wave, FlushFirst ff) {
+  const int si = segment_of(tabs, blockIdx.x);
+  const mirec_adam_table& T = tabs.t[si];
+  const int R = rows_per_wave.r[si];
+  const int lane = threadIdx.x & 63;
+  const int64_t r0 =
+      (((int64_t)blockIdx.x - tabs.block_start[si]) * (kAdamThreads / 64) + (threadIdx.x >> 6)) * R;
+  if (r0 >= T.n_rows) return;                          // wave-uniform
+  const int base = step_base[0] + step_off;
+  int raw = kZeroState, target = 0;
+  if (lane < R && r0 + lane < T.n_rows) {
+    const int f = ff.first[si][r0 + lane];
+    if (f > kFirstNotRead) {                           // (any negative value: not read)
+      target = base + f;
+      raw = T.last[r0 + lane];
+    }
+  }
+  uint64_t todo = __ballot(min(raw, target) < target);
+  while (todo) {                                       // wave-uniform loop over its rows
+    const int i = __builtin_ctzll(todo);
+    todo &= todo - 1;
+    flush_row<D>(T, r0 + i, __builtin_amdgcn_readfirstlane(__shfl(raw, i, 64)),
+                 __builtin_amdgcn_readfirstlane(__shfl(target, i, 64)), lane, consts, k);
+  }
+}
+
 // The masked flush's background form: a bounded grid of one-wave workgroups, made to run
 // beside other kernels. Wave w takes the row groups w, w + waves, ... of each table in
 // turn (kWalkRows consecutive rows: one bitmap word, a wave-uniform load), lists the
@@ -413,7 +453,7 @@ int launch_adam(Sched sched, const mirec_adam_table* tables, int32_t n_tables,
                 const int32_t* step_base, int32_t step_off, double beta1, double beta2,
                 double eps, double weight_decay, void* stream, const char* what,
                 const int32_t* flush_rows = nullptr, const FlushMasks* masks = nullptr,
-                int walk_waves = 0) {
+                int walk_waves = 0, const FlushFirst* firsts = nullptr) {
   if (n_tables < 1 || n_tables > kMaxTables || !tables || !consts || !step_base) {
     set_error("%s: bad arguments (n_tables=%d)", what, n_tables);
     return -1;
@@ -466,6 +506,14 @@ int launch_adam(Sched sched, const mirec_adam_table* tables, int32_t n_tables,
   FlushMasks fm;
   memset(&fm, 0, sizeof(fm));
   if (masks) fm = *masks;
+  // per-row targets (mirec_adam_flush_first_f32): the scan form's grid, unmasked
+  if (firsts && (sched != Sched::kFlush || !scan || masks)) {
+    set_error("%s: per-row targets need the flush with rows per wave and no mask", what);
+    return -1;
+  }
+  FlushFirst ff;
+  memset(&ff, 0, sizeof(ff));
+  if (firsts) ff = *firsts;
   AdamTables tabs;
   memset(&tabs, 0, sizeof(tabs));
   const bool deferred = sched == Sched::kDeferred;
@@ -556,6 +604,9 @@ int launch_adam(Sched sched, const mirec_adam_table* tables, int32_t n_tables,
     else if (DD >= 64 && walk)                                                               \
       hipLaunchKernelGGL(adam_flush_walk_kernel<(DD >= 64 ? DD : 64)>, grd, dim3(64), 0, st,   \
                          tabs, consts, step_base, step_off, k, fm);                          \
+    else if (DD >= 64 && scan && firsts)                                                     \
+      hipLaunchKernelGGL(adam_flush_first_kernel<(DD >= 64 ? DD : 64)>, grd, blk, 0, st, tabs, \
+                         consts, step_base, step_off, k, fr, ff);                            \
     else if (DD >= 64 && scan && masks)                                                      \
       hipLaunchKernelGGL((adam_flush_scan_kernel<(DD >= 64 ? DD : 64), true>), grd, blk, 0,    \
                          st, tabs, consts, step_base, step_off, k, fr, fm);                  \
@@ -695,6 +746,36 @@ extern "C" int mirec_adam_flush_masked_f32(const mirec_adam_table* tables, int32
   return launch_adam(Sched::kFlush, sel, n, nullptr, d, step_consts_dev, step_base_dev, step_off,
                      beta1, beta2, eps, weight_decay, stream, what,
                      rows_per_wave ? rows : nullptr, &fm, walk_waves);
+}
+
+extern "C" int mirec_adam_flush_first_f32(const mirec_adam_table* tables, int32_t n_tables,
+                                          int32_t d, const int32_t* const* first,
+                                          const int32_t* rows_per_wave,
+                                          const float* step_consts_dev,
+                                          const int32_t* step_base_dev, int32_t step_off,
+                                          double beta1, double beta2, double eps,
+                                          double weight_decay, void* stream) {
+  const char* what = "mirec_adam_flush_first_f32";
+  if (!tables || n_tables < 1 || n_tables > kMaxTables || !first || !rows_per_wave) {
+    set_error("%s: bad arguments (first-read arrays and rows per wave, per table)", what);
+    return -1;
+  }
+  // the tables that take part (first[q] == NULL: left out), in order
+  mirec_adam_table sel[kMaxTables];
+  int32_t rows[kMaxTables];
+  FlushFirst ff;
+  memset(&ff, 0, sizeof(ff));
+  int n = 0;
+  for (int q = 0; q < n_tables; ++q) {
+    if (!first[q]) continue;
+    sel[n] = tables[q];
+    rows[n] = rows_per_wave[q];
+    ff.first[n] = first[q];
+    ++n;
+  }
+  if (n == 0) return 0;
+  return launch_adam(Sched::kFlush, sel, n, nullptr, d, step_consts_dev, step_base_dev, step_off,
+                     beta1, beta2, eps, weight_decay, stream, what, rows, nullptr, 0, &ff);
 }
 
 extern "C" int mirec_adam_sparse_grad_f32(float* p, float* m, float* v, int64_t n_rows,

@@ -862,6 +862,41 @@ extern "C" int mirec_row_bitmap(const int64_t* keys, int64_t n_keys, int64_t n_r
   return launch_status(what);
 }
 
+namespace mirec {
+// first[row] = min(first[row], c) for every row of batch c's distinct-row list (grid:
+// x over the list, y = batch). Unsigned minimum: MIREC_FIRST_NOT_READ (-1) is the largest.
+__global__ __launch_bounds__(256) void first_read_kernel(const int32_t* __restrict__ uniq,
+                                                         const int32_t* __restrict__ n_uniq,
+                                                         int64_t per, int64_t n_rows,
+                                                         uint32_t* __restrict__ first) {
+  const int c = blockIdx.y;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= per || i >= n_uniq[c]) return;
+  const int64_t r = uniq[(int64_t)c * per + i];
+  if (r < 0 || r >= n_rows) return;
+  atomicMin(first + r, (uint32_t)c);
+}
+}  // namespace mirec
+
+extern "C" int mirec_first_read(const int32_t* uniq, const int32_t* n_uniq, int64_t n_batches,
+                                int64_t per, int64_t n_rows, int32_t* first, void* stream) {
+  const char* what = "mirec_first_read";
+  if (n_batches < 0 || n_batches > 32767 || per < 0 || per > INT32_MAX || n_rows <= 0 ||
+      !first || (n_batches > 0 && per > 0 && (!uniq || !n_uniq))) {
+    set_error("%s: bad arguments", what);
+    return -1;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  static_assert(MIREC_FIRST_NOT_READ == -1, "reset by bytes of 0xff");
+  const int rc = hip_status(hipMemsetAsync(first, 0xff, (size_t)n_rows * 4, st), what);
+  if (rc) return rc;
+  if (n_batches == 0 || per == 0) return 0;
+  hipLaunchKernelGGL(first_read_kernel, dim3((unsigned)((per + 255) / 256), (unsigned)n_batches),
+                     dim3(256), 0, st, uniq, n_uniq, per, n_rows,
+                     reinterpret_cast<uint32_t*>(first));
+  return launch_status(what);
+}
+
 #if defined(MIREC_STEP_COUNT)
 // diagnostic build only: copy (and clear) this unit's executed-work counters (16 x u64)
 extern "C" int mirec_work_counters(unsigned long long* dst, int clear) {

@@ -1,7 +1,8 @@
 """The chunk plan of the fused train step (trainer/fused.py) as pure integer
 arithmetic: which global batches form a chunk, which chunks start with an entry
-catch-up and end with a flush of the deferred Adam schedule, and how many rows
-per wave that flush runs. Nothing here touches a device (stdlib only)."""
+catch-up and end with a flush of the deferred Adam schedule, how many rows per
+wave that flush runs, and which chunks split that flush (background flush) or are
+preceded by the chunk advance. Nothing here touches a device (stdlib only)."""
 from __future__ import annotations
 
 import bisect
@@ -112,6 +113,36 @@ def masked_flush_rows(flush, nb, Bg, n_users, max_rows):
     while r * 2 <= max_rows and r * 2 * frac <= 1.0:
         r *= 2
     return (r,) + tuple(flush[1:])
+
+
+def advance_chunks(plan, Bg, adam_mode, fused_step, use_graph, min_steps=1, enabled=True):
+    """Per chunk of `plan`: is its captured graph preceded by the chunk advance (fused.py:
+    every row the chunk reads is brought to the step of its first read in one flush launch,
+    in place of the entry catch-up and of the look-ahead replays of those first reads)?
+    Only for a chunk of full batches on the one-GPU fused step (K35: `fused_step`) with the
+    deferred schedule and captured chunk graphs; never on the streamed, replicated or
+    sharded steps (their fused_step is False), which keep the entry catch-up and the step
+    kernel's own look-ahead. The advance is one more launch in front of the chunk's steps,
+    so the chunk has at least min_steps steps. The advance goes with the captured graph
+    only: a planned chunk that is entered mid-way, cut short or timed per kernel runs
+    eagerly, with the entry catch-up and the step kernel's look-ahead."""
+    on = bool(enabled and fused_step and use_graph and adam_mode == 'deferred')
+    return [bool(on and Bc == Bg and nb >= min_steps) for _, nb, Bc in plan]
+
+
+def advance_rows(nb, Bg, times, n_rows, max_rows):
+    """Rows per wave of a chunk's advance launch, per table (users, items), chosen as
+    masked_flush_rows chooses: the launch takes only the rows the chunk's nb batches read,
+    at most nb * Bg users and nb * (1 + times) * Bg items of the tables' n_rows, so R = the
+    largest power of two <= max_rows with R x that fraction <= 1."""
+    out = []
+    for per, rows in zip((Bg, (1 + times) * Bg), n_rows):
+        frac = min(1.0, nb * per / max(rows, 1))
+        r = 1
+        while r * 2 <= max_rows and r * 2 * frac <= 1.0:
+            r *= 2
+        out.append(r)
+    return tuple(out)
 
 
 def chunk_of(plan, b):

@@ -51,6 +51,12 @@ with its grouping), every row gets the same arithmetic from exactly one launch, 
 model side waits for the background's event before the next chunk or any read of the
 parameters. Which chunks get one is chunk_plan.bg_flush_chunks.
 
+Chunk advance: the rows a chunk does read are brought to the step of their first read in
+the chunk by one flush launch with a target per row, right before the chunk's graph (and
+its background flush), so the step kernel's look-ahead no longer replays those lags one
+wave per row inside every step (FusedBPRTrainStep.CHUNK_ADVANCE;
+chunk_plan.advance_chunks).
+
 The chunk plan (sizes, ramp, entry / flush flags) is trainer/chunk_plan.py; the
 row-sharded step is trainer/sharded.py and the evaluations are trainer/fused_eval.py
 (both re-exported here).
@@ -158,6 +164,7 @@ class _Slot(object):
         self.tab = tab or [_Lists(C, per, dev, ahead) for per in (Bg, KI)]
         self.records = None          # K35 row / contribution records (FusedBPRTrainStep)
         self.bitmap = None           # user rows the chunk reads, one bit per row (BG_FLUSH)
+        self.first = None            # per table: each row's first read in the chunk (CHUNK_ADVANCE)
         self.bg_done = None          # event after the chunk's background flush
         self.bg_busy = False         # a background flush was issued since the last refill
         self.prep = None             # mirec_chunk_prep descriptor (_chunk_prep)
@@ -246,9 +253,30 @@ class FusedBPRTrainStep(object):
     # at 3,072 (K35 loses more than the shorter background saves); 24.4 M without.
     BG_WAVES = int(os.environ.get('MIREC_BG_WAVES', '1536'))
     BG_MIN_STEPS = 32
-    # (RAMP, FLUSH_EVERY, FLUSH_SPARSE_MAX_ROWS, MAIN_FIRST, BG_FLUSH, BG_WAVES and
-    # BG_MIN_STEPS are read at begin_epoch / when a chunk is entered: an instance may set
-    # its own after construction)
+    # Chunk advance (one GPU, K35, deferred schedule, captured chunk graphs): right before a
+    # chunk's graph, one flush launch with a target per row (mirec_adam_flush_first_f32)
+    # brings every row the chunk reads to the step of its FIRST read in the chunk (the
+    # first-read table is built with the grouping: mirec_first_read). Those steps have a
+    # zero gradient by construction, so the state is the one K35's look-ahead would reach one
+    # launch before the read — but replayed by a flush grid (the whole chip) instead of by
+    # ~500 long serial chains inside each latency-bound K35 launch, whose duration grew with
+    # the position in the chunk (C2: 12 -> 21 us over 64 steps; with the advance 10 -> 14).
+    # K35's look-ahead skips a row that is already complete (last > step), so the advance
+    # replaces the entry catch-up and those replays and nothing else changes; bit-identical
+    # (zero-gradient replay is split-invariant). It is launched on the model stream AHEAD of
+    # the graph and of the chunk's background flush (which follows the model-side work
+    # enqueued so far): as the graph's first node it ran beside the background flush and took
+    # 150-480 us instead of ~100, and stretched that flush past the chunk's end.
+    # MIREC_CHUNK_ADVANCE=0: the entry catch-up and K35's own look-ahead only.
+    # ADV_MIN_STEPS: the shortest chunk that gets one. The launch is ~50 us for 16 steps and
+    # ~100 us for 64, serial in front of the chunk's steps, and K35 only slows late in a
+    # chunk: C2's driver window (chunks of 8 and 12) lost 3-7 % with it, 16 / 32 / 64 did not
+    # differ on the default window.
+    CHUNK_ADVANCE = os.environ.get('MIREC_CHUNK_ADVANCE', '1') != '0'
+    ADV_MIN_STEPS = 32
+    # (RAMP, FLUSH_EVERY, FLUSH_SPARSE_MAX_ROWS, MAIN_FIRST, BG_FLUSH, BG_WAVES, BG_MIN_STEPS,
+    # CHUNK_ADVANCE and ADV_MIN_STEPS are read at begin_epoch / when a chunk is entered: an
+    # instance may set its own after construction)
 
     def __init__(self, model, optimizer, train_data, chunk=None, use_graph=True,
                  adam_mode='deferred', dist=None, fused_step=None):
@@ -314,6 +342,7 @@ class FusedBPRTrainStep(object):
         self.n_batches = 0
         self._plan, self._flags, self._flush_at = [], [], set()
         self._bg = []               # per chunk: flush split into background + masked (BG_FLUSH)
+        self._adv = []              # per chunk: its graph starts with the advance (CHUNK_ADVANCE)
         self._bg_pending = None     # event of a background flush the model side has not awaited
         self._bg_mark = torch.cuda.Event()   # model-side work a background flush follows
         self._bg_mark.record(torch.cuda.current_stream(dev))
@@ -356,6 +385,8 @@ class FusedBPRTrainStep(object):
                 sl.records = [torch.empty(self.C * w, dtype=torch.int32, device=dev)
                               for w in self._rec_ints(self.Bg)]
                 sl.bitmap = torch.zeros((self.nU + 31) // 32, dtype=torch.int32, device=dev)
+                sl.first = [torch.full((n,), -1, dtype=torch.int32, device=dev)
+                            for n in (self.nU, self.nI)]
                 sl.bg_done = torch.cuda.Event()
                 sl.bg_done.record(torch.cuda.current_stream(dev))
             # split rows' hand-off scratch (one launch at a time on the compute stream)
@@ -495,6 +526,13 @@ class FusedBPRTrainStep(object):
             check(lib().mirec_row_bitmap(slot.user_keys.data_ptr(), nb * Bc, self.nU,
                                          slot.bitmap.data_ptr(), st.cuda_stream),
                   'mirec_row_bitmap')
+        if slot.first is not None and self._adv[self._chunk_of(b0)]:
+            # each row's first read in the chunk, per table, for the chunk's advance
+            for l, per, n, first in zip(slot.tab, (Bc, (1 + self.times) * Bc),
+                                        (self.nU, self.nI), slot.first):
+                check(lib().mirec_first_read(l.uniq.data_ptr(), l.nu.data_ptr(), nb, per, n,
+                                             first.data_ptr(), st.cuda_stream),
+                      'mirec_first_read')
         slot.ready.record(st)
         slot.group_pending = False
 
@@ -768,6 +806,17 @@ class FusedBPRTrainStep(object):
         t[0].rows = t[1].rows = self.xbuf.data_ptr()
         self._adam(stream, -1, t, 'ahead')
 
+    def _advance(self, slot, stream, nb):
+        """The chunk advance (launched right before a chunk's graph, in place of the graph's
+        entry catch-up): every row the nb batches of `slot` read, of both tables, from
+        wherever it lags to step_idx + its first read in the chunk (slot.first). Rows the
+        chunk does not read are not touched (the chunk's background flush completes them)."""
+        rows = chunk_plan.advance_rows(nb, self.Bg, self.times, (self.nU, self.nI),
+                                       self.FLUSH_SPARSE_MAX_ROWS)
+        self._launch('advance', stream, 'mirec_adam_flush_first_f32', self._tables, 2, self.d,
+                     (ctypes.c_void_p * 2)(*[f.data_ptr() for f in slot.first]),
+                     (ctypes.c_int32 * 2)(*rows), *self._sched(0))
+
     def _grad_scale(self, Bc):
         """1 / (rows of the GLOBAL batch): the reference's .mean() over the batch."""
         R = Bc * self.times
@@ -776,20 +825,22 @@ class FusedBPRTrainStep(object):
             self._gs = float(np.float32(1.0) / np.float32(R))
         return self._gs
 
-    def _graph_for(self, slot, nb, entry, flush, masked=False):
+    def _graph_for(self, slot, nb, entry, flush, masked=False, advance=False):
         """HIP graph of the model-side steps of an nb-batch chunk in `slot`, with
         the entry catch-up and / or the closing flush — `masked`: its foreground half
-        (_flush_masked) — captured once per (slot, nb, entry, flush, masked); capture
-        synchronizes, so begin_epoch captures every variant its plan uses before any
-        batch runs. One chain of launches: no parallel branches."""
-        key = (nb, entry, flush, masked)
+        (_flush_masked); `advance`: no entry catch-up, run_batches launches the chunk
+        advance ahead of the graph (_advance: it covers the entry catch-up's rows) —
+        captured once per (slot, nb, entry, flush, masked, advance); capture synchronizes,
+        so begin_epoch captures every variant its plan uses before any batch runs. One
+        chain of launches: no parallel branches."""
+        key = (nb, entry, flush, masked, advance)
         g = slot.graphs.get(key)
         if g is None:
             g = torch.cuda.CUDAGraph()
             cap = torch.cuda.Stream(device=self.device)
             cap.wait_stream(torch.cuda.current_stream(self.device))
             with torch.cuda.graph(g, stream=cap):
-                if entry:
+                if entry and not advance:
                     self._entry(slot, cap)
                 for c in range(nb):
                     self._step(slot, c, self.Bg, cap, c, c + 1 < nb)
@@ -804,15 +855,16 @@ class FusedBPRTrainStep(object):
         return g
 
     def _capture_variants(self):
-        """Capture the model-side graph of every (slot, size, entry, flush, masked)
+        """Capture the model-side graph of every (slot, size, entry, flush, masked, advance)
         variant the epoch's chunk plan uses."""
         S = len(self.slots)
         # flush flags are False, True or a tuple of row counts: sort by their repr
-        variants = sorted({(k % S, n, e, f, bg) for k, ((_, n, Bc), (e, f), bg) in
-                           enumerate(zip(self._plan, self._flags, self._bg)) if Bc == self.Bg},
-                          key=lambda v: (v[0], v[1], v[2], repr(v[3]), v[4]))
-        for k, n, e, f, bg in variants:
-            self._graph_for(self.slots[k], n, e, f, bg)
+        variants = sorted({(k % S, n, e, f, bg, adv) for k, ((_, n, Bc), (e, f), bg, adv) in
+                           enumerate(zip(self._plan, self._flags, self._bg, self._adv))
+                           if Bc == self.Bg},
+                          key=lambda v: (v[0], v[1], v[2], repr(v[3]), v[4], v[5]))
+        for k, n, e, f, bg, adv in variants:
+            self._graph_for(self.slots[k], n, e, f, bg, adv)
 
     # ------------------------------------------------------------------ epoch API
     def begin_epoch(self, cuts=(), hold_prep_from=None, flush_at=()):
@@ -871,7 +923,10 @@ class FusedBPRTrainStep(object):
         self._bg = chunk_plan.bg_flush_chunks(self._plan, self._flags, self.Bg, self.adam_mode,
                                               self.fused_step, self.use_graph,
                                               self.BG_MIN_STEPS, self.BG_FLUSH)
-        if self.use_graph:                      # capture up front: capture synchronizes
+        self._adv = chunk_plan.advance_chunks(self._plan, self.Bg, self.adam_mode,
+                                              self.fused_step, self.use_graph,
+                                              self.ADV_MIN_STEPS, self.CHUNK_ADVANCE)
+        if self.use_graph:                     # capture up front: capture synchronizes
             self._capture_variants()
         self.prep_stream.wait_stream(torch.cuda.current_stream(self.device))
         self._last_walked = None               # event after the latest issued walk
@@ -974,9 +1029,11 @@ class FusedBPRTrainStep(object):
             self._enter_chunk(k, stream)
             slot = self.slots[k % len(self.slots)]
             c0, c1 = b - b0, min(nb, b_end - b0)
-            key = (nb, entry, flush, self._bg[k])
+            key = (nb, entry, flush, self._bg[k], self._adv[k])
             if (self.use_graph and c0 == 0 and c1 == nb and Bc == self.Bg
                     and self.kernel_events is None and key in slot.graphs):
+                if self._adv[k]:               # ahead of the background flush and the graph
+                    self._advance(slot, stream, nb)
                 if chunk_plan.bg_flush_now(self._bg[k], c0, c1, nb, key in slot.graphs,
                                            self.kernel_events is not None):
                     self._flush_background(slot, b0 + nb, stream)
