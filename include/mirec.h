@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define MIREC_ABI_VERSION 19
+#define MIREC_ABI_VERSION 20
 
 int mirec_abi_version(void);
 const char* mirec_last_error(void);
@@ -733,6 +733,37 @@ int mirec_fullsort_topk_split_f32(const float* Uq, int64_t nq, const float* EI, 
  * full_sort_predict API contract (flat [nq*I] scores, bpr.py:91-96). */
 int mirec_score_matrix_f32(const float* Uq, int64_t nq, const float* EI, int64_t I,
                            int32_t d, float* S, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * K12  Full-catalogue cross entropy, fused (no [B, I] logits matrix).
+ * Replaces, for loss_type 'CE' (sasrec.py:135-141), torch.matmul(seq_output,
+ *   item_embedding.weight^T) + nn.CrossEntropyLoss (mean) and their autograd backward.
+ * S[B, d] sequence outputs; E[I, d] the item table, ALL rows (row 0 included, as in the
+ *   reference); target[B] int64 in [0, I). target is only ever COMPARED with item ids,
+ *   never used as an index: a target outside [0, I) causes no out-of-range access and
+ *   leaves that row's loss unspecified.
+ * Forward:  lse[b] = logsumexp_i <S[b], E[i]>;  loss_rows[b] = lse[b] - <S[b], E[target[b]]>
+ *   (the caller takes the mean).
+ * Backward: with w[b,i] = (exp(<S[b],E[i]> - lse[b]) - [i == target[b]]) * g_dev[0] / B
+ *   (g_dev: the incoming gradient of the mean loss, a DEVICE scalar: no host sync):
+ *   gS[b] = sum_i w[b,i] E[i];  dE[i] = sum_b w[b,i] S[b]  — every row of dE is written.
+ * splits: the item range is split over `splits` workgroups per query block (partials in
+ *   the workspace, folded in ascending split order). 0 = auto, a pure function of
+ *   (B, I, d); an explicit value is clamped so that a span is a whole number of 64-item
+ *   tiles and at least one. mirec_full_ce_splits returns the number actually used. The
+ *   workspace size is for the same (B, I, d, splits) and serves both calls.
+ * FP32 MFMA, exact f32 products; no atomics: every sum has one owner and a fixed order.
+ * d in {32, 64, 128, 256}. B == 0 returns 0.
+ * ------------------------------------------------------------------------- */
+int32_t mirec_full_ce_splits(int64_t B, int64_t I, int32_t d, int32_t splits);
+size_t mirec_full_ce_workspace_size(int64_t B, int64_t I, int32_t d, int32_t splits);
+int mirec_full_ce_fwd_f32(const float* S, int64_t B, const float* E, int64_t I, int32_t d,
+                          const int64_t* target, int32_t splits, float* lse,
+                          float* loss_rows, void* workspace, void* stream);
+int mirec_full_ce_bwd_f32(const float* S, int64_t B, const float* E, int64_t I, int32_t d,
+                          const int64_t* target, const float* lse, const float* g_dev,
+                          int32_t splits, float* gS, float* dE, void* workspace,
+                          void* stream);
 
 /* ---------------------------------------------------------------------------
  * K7  Graph propagation (LightGCN): CSR SpMM with a fused epilogue.

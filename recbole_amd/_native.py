@@ -240,6 +240,12 @@ SIGNATURES = {
                                               c_int32, c_int32, _P, ctypes.c_size_t, _P, _P, _P,
                                               _P]),
     "mirec_score_matrix_f32": (c_int, [_P, c_int64, _P, c_int64, c_int32, _P, _P]),
+    "mirec_full_ce_splits": (c_int32, [c_int64, c_int64, c_int32, c_int32]),
+    "mirec_full_ce_workspace_size": (c_size_t, [c_int64, c_int64, c_int32, c_int32]),
+    "mirec_full_ce_fwd_f32": (c_int, [_P, c_int64, _P, c_int64, c_int32, _P, c_int32, _P, _P, _P,
+                                      _P]),
+    "mirec_full_ce_bwd_f32": (c_int, [_P, c_int64, _P, c_int64, c_int32, _P, _P, _P, c_int32, _P,
+                                      _P, _P, _P]),
     "mirec_spmm_csr_f32": (c_int, [_P, _P, _P, c_int64, c_int32, _P, _P, _P, c_int64, c_int32,
                                    _P, _P, c_int64, _P, ctypes.POINTER(RowsRef),
                                    ctypes.POINTER(SpmmEpilogue), _P]),
@@ -292,7 +298,7 @@ SIGNATURES = {
     "mirec_gather_scale_rows_f32": (c_int, [_P, c_int64, c_int32, _P, c_int64, _P, _P, _P]),
 }
 
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 
 class NativeError(RuntimeError):

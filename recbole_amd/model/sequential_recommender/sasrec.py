@@ -9,8 +9,10 @@ losses run in hand-written gfx950 kernels:
 * loss_type 'BPR' (:126-134)  -> K3 fused dot + BPR + gradients on seq_output;
 * loss_type 'SSM' (build extension for the C3 configuration: sampled softmax
   over the positive and neg_sample_num sampled negatives) -> K9b;
-* loss_type 'CE' (:135-141)   -> full-vocabulary logits on the library GEMM +
-  cross entropy (the reference's op sequence);
+* loss_type 'CE' (:135-141)   -> ce_kernel 'library' (the default): full-vocabulary
+  logits on the library GEMM + cross entropy (the reference's op sequence);
+  ce_kernel 'fused': K12, the logits formed tile by tile on FP32 MFMA and consumed
+  by an online log-sum-exp, recomputed in the backward (no [B, n_items] matrix);
 * full_sort_predict            -> FP32-MFMA score matrix; the trainer's fused
   evaluator ranks seq_output against all items with K6 (no score matrix).
 The transformer encoder between them is the reference's op sequence on torch
@@ -176,10 +178,37 @@ class _SampledSoftmaxFn(torch.autograd.Function):
         return gS * g, _item_grad(ctx, gI * g, items), None, None
 
 
+class _FullCEFn(torch.autograd.Function):
+    """mean_b [logsumexp_i <s_b, E_i> - <s_b, E_target_b>] over ALL rows of E, the padding
+    row included as in the reference (K12: no [B, n_items] logits matrix). The backward
+    recomputes the logits and returns the dense item-table gradient."""
+
+    @staticmethod
+    def forward(ctx, S, E, target, splits=0):
+        B = S.shape[0]
+        Sd = S.detach().contiguous()
+        tgt = target.contiguous()
+        lse, loss_rows = ops.full_ce_fwd(Sd, E.detach(), tgt, splits)
+        ctx.save_for_backward(Sd, E, tgt, lse)
+        ctx.splits = splits
+        return ops.fixed_sum(loss_rows).view(()) / B
+
+    @staticmethod
+    def backward(ctx, g):
+        S, E, tgt, lse = ctx.saved_tensors
+        # the incoming gradient stays on the device (no host sync)
+        g = g.detach().to(torch.float32).reshape(1).contiguous()
+        gS, dE = ops.full_ce_bwd(S, E.detach(), tgt, lse, g, ctx.splits)
+        return gS, dE, None, None
+
+
+CE_WIDTHS = (32, 64, 128, 256)          # K12's hidden sizes (as K6)
+
+
 class SASRec(SequentialRecommender):
 
     # the training step has no host synchronisation or host-side branching on device
-    # values (K9a / K9b / K3 launches with host-known sizes, deferred catch-ups on the
+    # values (K9a / K9b / K3 / K12 launches with host-known sizes, deferred catch-ups on the
     # device step counter, dropout draws keyed by device counters the kernels advance): the
     # trainer may capture it in a HIP graph (trainer/graph_step.py)
     graph_step_safe = True
@@ -196,6 +225,11 @@ class SASRec(SequentialRecommender):
         self.layer_norm_eps = config['layer_norm_eps']
         self.initializer_range = config['initializer_range']
         self.loss_type = config['loss_type']
+        # 'CE' only: 'library' (default) = the reference's matmul + CrossEntropyLoss;
+        # 'fused' = K12 where it applies (CUDA fp32, hidden_size in CE_WIDTHS)
+        self.ce_kernel = config['ce_kernel'] if config['ce_kernel'] is not None else 'library'
+        if self.ce_kernel not in ('library', 'fused'):
+            raise ValueError(f"ce_kernel must be 'library' or 'fused', got {self.ce_kernel!r}")
         self.item_embedding = nn.Embedding(self.n_items, self.hidden_size, padding_idx=0)
         self.position_embedding = nn.Embedding(self.max_seq_length, self.hidden_size)
         self.trm_encoder = TransformerEncoder(
@@ -272,6 +306,10 @@ class SASRec(SequentialRecommender):
         if self.loss_type == 'SSM':
             return _SampledSoftmaxFn.apply(seq_output, W, pos_items,
                                            interaction[self.NEG_ITEM_ID])
+        if (self.ce_kernel == 'fused' and seq_output.is_cuda
+                and seq_output.dtype == torch.float32 and W.dtype == torch.float32
+                and self.hidden_size in CE_WIDTHS):
+            return _FullCEFn.apply(seq_output, W, pos_items)
         logits = torch.matmul(seq_output, W.transpose(0, 1))
         return self.loss_fct(logits, pos_items)
 

@@ -1004,6 +1004,55 @@ def score_matrix(Uq, EI, out=None):
     return out
 
 
+# ---------------------------------------------------------------- K12 full-catalogue CE
+def full_ce_splits(B: int, I: int, d: int, splits: int = 0) -> int:
+    """The item split K12 uses for `splits` (0 = auto): a host-side pure function."""
+    return int(lib().mirec_full_ce_splits(B, I, d, splits))
+
+
+def _full_ce_ws(S, E, splits):
+    n = lib().mirec_full_ce_workspace_size(S.shape[0], E.shape[0], S.shape[1], splits)
+    return torch.empty(n, dtype=torch.uint8, device=S.device)
+
+
+def full_ce_fwd(S, E, target, splits: int = 0):
+    """K12a: (lse[B], loss_rows[B]) of the logits S @ E^T against `target`, without the
+    [B, I] matrix; loss_rows = lse - logit of the target."""
+    _dev(S, torch.float32, "S")
+    _dev(E, torch.float32, "E")
+    _dev(target, torch.int64, "target")
+    B, d = S.shape
+    if E.shape[1] != d or target.numel() != B:
+        raise ValueError("full_ce_fwd: shapes differ")
+    lse = torch.empty(B, dtype=torch.float32, device=S.device)
+    loss_rows = torch.empty(B, dtype=torch.float32, device=S.device)
+    ws = _full_ce_ws(S, E, splits)
+    rc = lib().mirec_full_ce_fwd_f32(ptr(S), B, ptr(E), E.shape[0], d, ptr(target), splits,
+                                     ptr(lse), ptr(loss_rows), ptr(ws), stream_handle())
+    check(rc, "mirec_full_ce_fwd_f32")
+    return lse, loss_rows
+
+
+def full_ce_bwd(S, E, target, lse, g, splits: int = 0):
+    """K12b + K12c: (gS[B, d], dE[I, d]) of the mean cross entropy for the incoming
+    gradient `g`, a one-element device tensor (read on the device: no host sync)."""
+    _dev(S, torch.float32, "S")
+    _dev(E, torch.float32, "E")
+    _dev(target, torch.int64, "target")
+    _dev(lse, torch.float32, "lse")
+    _dev(g, torch.float32, "g")
+    B, d = S.shape
+    if E.shape[1] != d or target.numel() != B or lse.numel() != B or g.numel() != 1:
+        raise ValueError("full_ce_bwd: shapes differ")
+    gS = torch.empty(B, d, dtype=torch.float32, device=S.device)
+    dE = torch.empty(E.shape[0], d, dtype=torch.float32, device=S.device)   # every row written
+    ws = _full_ce_ws(S, E, splits)
+    rc = lib().mirec_full_ce_bwd_f32(ptr(S), B, ptr(E), E.shape[0], d, ptr(target), ptr(lse),
+                                     ptr(g), splits, ptr(gS), ptr(dE), ptr(ws), stream_handle())
+    check(rc, "mirec_full_ce_bwd_f32")
+    return gS, dE
+
+
 # ---------------------------------------------------------------- K7 graph propagation
 def _rows_ref(t):
     """mirec_rows_ref from None, a [n, d] tensor, or a (lo, hi) pair of row blocks."""

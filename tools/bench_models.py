@@ -6,6 +6,9 @@ C2 headline (bench.py): one JSON line per configuration, 1 GPU.
       (RepeatableSampler, K4), sampled-softmax loss (K9b), dense Adam over every
       parameter (the reference's optim.Adam on nn.Embedding(sparse=False)).
       Unit: sequences/s; dominant-kernel rooflines from HIP events.
+      --c3-loss CE-library / CE-fused: the same step with the reference's default
+      full-catalogue cross entropy (no negatives drawn), on the library GEMM path or on
+      K12 (ce_kernel='fused'); the record carries the peak allocated memory.
   C4  DeepFM, Criteo shape: 13 float + 26 token fields, vocabularies summing to
       33,000,000 (10M, 8M, 5M, 4M, 3M, then geometric down to 3), Zipf(1.1) ids,
       d = 16, MLP 624-128-128-128-1 (dropout 0.2), BCE, B = 2,048, dense Adam.
@@ -327,7 +330,14 @@ def bench_c4(dev, steps, warmup, scale=1.0, B=2048, d=16, n_batches=16):
 
 
 # ----------------------------------------------------------------------------- C3
-def bench_c3(dev, steps, warmup, scale=1.0, B=2048, L=50, d=128, n_neg=100, n_batches=8):
+C3_LOSSES = ('SSM', 'CE-library', 'CE-fused')
+
+
+def bench_c3(dev, steps, warmup, scale=1.0, B=2048, L=50, d=128, n_neg=100, n_batches=8,
+             loss='SSM'):
+    if loss not in C3_LOSSES:
+        raise ValueError(f'loss must be one of {C3_LOSSES}')
+    ce = loss != 'SSM'
     from recbole_amd import ops
     from recbole_amd.config import Config
     from recbole_amd.data.interaction import Interaction
@@ -337,7 +347,9 @@ def bench_c3(dev, steps, warmup, scale=1.0, B=2048, L=50, d=128, n_neg=100, n_ba
     n_items = max(1000, int(3_000_000 * scale)) + 1
     config = Config(model='SASRec', dataset='books-synth', config_dict={
         'hidden_size': d, 'inner_size': 256, 'n_layers': 2, 'n_heads': 2,
-        'MAX_ITEM_LIST_LENGTH': L, 'loss_type': 'SSM', 'training_neg_sample_num': n_neg,
+        'MAX_ITEM_LIST_LENGTH': L, 'loss_type': 'CE' if ce else 'SSM',
+        'training_neg_sample_num': 0 if ce else n_neg,
+        'ce_kernel': {'CE-library': 'library', 'CE-fused': 'fused'}.get(loss),
         'state': 'ERROR', 'data_path': ROOT})
     config['device'] = dev
     torch.manual_seed(2020)
@@ -370,9 +382,11 @@ def bench_c3(dev, steps, warmup, scale=1.0, B=2048, L=50, d=128, n_neg=100, n_ba
     def step():
         b = batches[it[0] % n_batches]
         it[0] += 1
-        # the data side (the loader's K4 walk of 100 negatives per sequence) stays eager
-        neg = ops.sample_walk(random_list, pr, b['user_id'], n_neg, None, None, 1_000_000, False)
-        b.interaction['neg_item_id'] = neg
+        if not ce:
+            # the data side (the loader's K4 walk of 100 negatives per sequence) stays eager
+            neg = ops.sample_walk(random_list, pr, b['user_id'], n_neg, None, None, 1_000_000,
+                                  False)
+            b.interaction['neg_item_id'] = neg
         if gs is not None:
             gs.step(b)
             return
@@ -381,6 +395,9 @@ def bench_c3(dev, steps, warmup, scale=1.0, B=2048, L=50, d=128, n_neg=100, n_ba
         loss.backward()
         opt.step()
 
+    if ce:
+        return _c3_ce_record(dev, step, opt, model, batches, loss, steps, warmup, n_items, B, L,
+                             d)
     t = _timed(step, steps, warmup, opt)
     from recbole_amd.model.sequential_recommender.sasrec import _SampledSoftmaxFn
     b0 = batches[0]
@@ -464,6 +481,67 @@ def bench_c3(dev, steps, warmup, scale=1.0, B=2048, L=50, d=128, n_neg=100, n_ba
                              'the backward (S recomputed, dV, dP, dQ, dK)'},
         'k9b': _k9b_line(d, n_neg, k9_bytes, tk),
     }
+
+
+def _c3_ce_record(dev, step, opt, model, batches, loss, steps, warmup, n_items, B, L, d):
+    """The C3 step with the full-catalogue cross entropy: sequences/s, the peak allocated
+    memory of the run (measured before the loss-only timings below), and the loss's own forward / backward call times (HIP
+    events, host-inclusive; the per-kernel split of K12a / K12b / K12c comes from a kernel
+    trace of this leg, tools/step_breakdown.py). One GEMM pass over the logits is
+    2 * B * I * d FLOPs: the library path makes 3 (logits, dS, dE), K12 makes 5 (K12a 1,
+    K12b 2, K12c 2: each backward kernel recomputes its logits tile)."""
+    from recbole_amd import ops
+    t = _timed(step, steps, warmup, opt)
+    # over the whole run, the warm-up included: the captured step allocates while it is
+    # captured (its replays reuse that pool and allocate nothing)
+    peak = torch.cuda.max_memory_allocated(dev)
+    reserved = torch.cuda.max_memory_reserved(dev)
+    gemm = 2 * B * n_items * d
+    S = torch.randn(B, d, device=dev) * 0.05
+    W = model.item_embedding.weight.detach()
+    tgt = batches[0]['item_id']
+    rec = {
+        'config': 'C3', 'loss': loss, 'metric': 'train sequences/s', 'value': round(B / t, 1),
+        'unit': 'sequences/s', 'ms_per_step': round(t * 1e3, 3), 'batch': B, 'steps': steps,
+        'adam_mode': ADAM_MODE, 'graph_step': GRAPH_STEP,
+        'workload': f'SASRec Amazon-Books-shape: {n_items:,} items (incl. PAD), L={L}, d={d}, '
+                    f'2 layers x 2 heads, inner 256, full-catalogue cross entropy ({loss}), '
+                    f'dense Adam',
+        'dtype': 'fp32',
+        'peak_allocated_MB': round(peak / 1e6, 1),
+        'peak_reserved_MB': round(reserved / 1e6, 1),
+        'logits_matrix_MB': round(B * n_items * 4 / 1e6, 1),
+        'gemm_pass_gflop': round(gemm / 1e9, 2),
+    }
+    if loss == 'CE-fused':
+        g1 = torch.ones(1, device=dev)
+        lse, _ = ops.full_ce_fwd(S, W, tgt)
+        tf = _event_time(lambda: ops.full_ce_fwd(S, W, tgt))
+        tb = _event_time(lambda: ops.full_ce_bwd(S, W, tgt, lse, g1))
+        rec['k12'] = {
+            'splits': ops.full_ce_splits(B, n_items, d, 0),
+            'fwd_call_us': round(tf * 1e6, 1), 'bwd_call_us': round(tb * 1e6, 1),
+            'fwd_tflops': round(gemm / tf / 1e12, 2), 'bwd_tflops': round(4 * gemm / tb / 1e12, 2),
+            'fwd_frac_of_peak': round(gemm / tf / 1e12 / MFMA_F32_PEAK_TFLOPS, 4),
+            'bwd_frac_of_peak': round(4 * gemm / tb / 1e12 / MFMA_F32_PEAK_TFLOPS, 4),
+            'timing': 'HIP events around one ops.full_ce_fwd (K12a + finish) and one '
+                      'ops.full_ce_bwd (K12b + partial sum + K12c), median of 10, '
+                      'host-inclusive; FLOPs 1 and 4 GEMM passes of 2*B*I*d'}
+    else:
+        Sg = S.clone().requires_grad_()
+        Wg = W.clone().requires_grad_()
+
+        def lib_ce():
+            l_ = torch.nn.functional.cross_entropy(torch.matmul(Sg, Wg.transpose(0, 1)), tgt)
+            torch.autograd.grad(l_, (Sg, Wg))
+        lib_ce()
+        tl = _event_time(lib_ce)
+        rec['library_ce'] = {
+            'fwd_bwd_call_us': round(tl * 1e6, 1),
+            'tflops': round(3 * gemm / tl / 1e12, 2),
+            'timing': 'HIP events around matmul + cross_entropy + autograd.grad, median of '
+                      '10, host-inclusive; FLOPs 3 GEMM passes of 2*B*I*d'}
+    return rec
 
 
 def _k9b_line(d, n_neg, k9_bytes, tk):
@@ -591,6 +669,9 @@ def main():
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--adam-mode', default='deferred', choices=['deferred', 'streamed'])
     ap.add_argument('--eager-step', action='store_true', help='C3 / C4 without the captured step')
+    ap.add_argument('--c3-loss', default='SSM', choices=list(C3_LOSSES),
+                    help='C3 loss: sampled softmax (default) or the full-catalogue cross '
+                         'entropy on the library path / on K12')
     args = ap.parse_args()
     global CPU_BASELINE, ADAM_MODE, GRAPH_STEP
     CPU_BASELINE = not args.no_cpu_baseline
@@ -600,7 +681,7 @@ def main():
     res = []
     for c in args.configs.split(','):
         if c == 'C3':
-            r = bench_c3(dev, args.steps, args.warmup, args.scale)
+            r = bench_c3(dev, args.steps, args.warmup, args.scale, loss=args.c3_loss)
         elif c == 'C4':
             r = bench_c4(dev, args.steps, args.warmup, args.scale)
         elif c == 'C5':
