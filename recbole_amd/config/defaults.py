@@ -1,6 +1,6 @@
 """Default configuration values, restated as Python data from the reference's
 property files (recbole/properties/overall.yaml, dataset/sample.yaml,
-dataset/ml-100k.yaml, model/{BPR,LightGCN,SASRec,DeepFM}.yaml,
+dataset/ml-100k.yaml, model/{BPR,LightGCN,SASRec,GRU4Rec,DeepFM}.yaml,
 quick_start_config/{sequential,context-aware}.yaml)."""
 from recbole_amd.utils.enum_type import ModelType
 
@@ -59,6 +59,8 @@ MODEL_DEFAULTS = {
     'SASRec': dict(n_layers=2, n_heads=2, hidden_size=64, inner_size=256,
                    hidden_dropout_prob=0.5, attn_dropout_prob=0.5, hidden_act='gelu',
                    layer_norm_eps=1e-12, initializer_range=0.02, loss_type='CE'),
+    'GRU4Rec': dict(embedding_size=64, hidden_size=128, num_layers=1, dropout_prob=0.3,
+                    loss_type='CE'),
     'DeepFM': dict(embedding_size=10, mlp_hidden_size=[128, 128, 128], dropout_prob=0.2),
 }
 

@@ -9,6 +9,10 @@ C2 headline (bench.py): one JSON line per configuration, 1 GPU.
       --c3-loss CE-library / CE-fused: the same step with the reference's default
       full-catalogue cross entropy (no negatives drawn), on the library GEMM path or on
       K12 (ce_kernel='fused'); the record carries the peak allocated memory.
+      --c3-model GRU4Rec: the same batches and item table through GRU4Rec at the
+      reference's default widths (E = 64, H = 128), run eagerly (the model does not
+      offer its step for capture); GRU4Rec has no sampled softmax, so the default loss there is BPR with one
+      walk negative per sequence (--c3-loss CE-library / CE-fused as for SASRec).
   C4  DeepFM, Criteo shape: 13 float + 26 token fields, vocabularies summing to
       33,000,000 (10M, 8M, 5M, 4M, 3M, then geometric down to 3), Zipf(1.1) ids,
       d = 16, MLP 624-128-128-128-1 (dropout 0.2), BCE, B = 2,048, dense Adam.
@@ -483,6 +487,82 @@ def bench_c3(dev, steps, warmup, scale=1.0, B=2048, L=50, d=128, n_neg=100, n_ba
     }
 
 
+def bench_c3_gru4rec(dev, steps, warmup, scale=1.0, B=2048, L=50, E=64, H=128, n_batches=8,
+                     loss='SSM'):
+    """The C3-shaped step (bench_c3's batches: Zipf(1.1) items, Poisson(20)+4 lengths, the
+    3,000,000-row item table) through GRU4Rec: BPR with one walk negative per sequence
+    (loss 'SSM': GRU4Rec has no sampled softmax) or the full-catalogue cross entropy."""
+    if loss not in C3_LOSSES:
+        raise ValueError(f'loss must be one of {C3_LOSSES}')
+    ce = loss != 'SSM'
+    from recbole_amd import ops
+    from recbole_amd.config import Config
+    from recbole_amd.data.interaction import Interaction
+    from recbole_amd.model.sequential_recommender import GRU4Rec
+    from recbole_amd.trainer.optim import FusedAdam
+    from recbole_amd.utils import FeatureType
+    n_items = max(1000, int(3_000_000 * scale)) + 1
+    config = Config(model='GRU4Rec', dataset='books-synth', config_dict={
+        'embedding_size': E, 'hidden_size': H, 'MAX_ITEM_LIST_LENGTH': L,
+        'loss_type': 'CE' if ce else 'BPR', 'training_neg_sample_num': 0 if ce else 1,
+        'ce_kernel': {'CE-library': 'library', 'CE-fused': 'fused'}.get(loss),
+        'state': 'ERROR', 'data_path': ROOT})
+    config['device'] = dev
+    torch.manual_seed(2020)
+    model = GRU4Rec(config, StubDataset({'item_id': FeatureType.TOKEN},
+                                        {'item_id': n_items})).to(dev)
+    rng = np.random.default_rng(2020)
+    batches = []
+    for _ in range(n_batches):
+        lens = np.minimum(rng.poisson(20, B) + 4, L).astype(np.int64)
+        seq = np.zeros((B, L), dtype=np.int64)
+        ids = _zipf_ids(rng, 1.1, int(lens.sum()), n_items - 1)
+        mask = np.arange(L)[None, :] < lens[:, None]
+        seq[mask] = ids
+        batches.append(Interaction({
+            'item_id_list': torch.as_tensor(seq), 'item_length': torch.as_tensor(lens),
+            'item_id': torch.as_tensor(_zipf_ids(rng, 1.1, B, n_items - 1)),
+            'user_id': torch.as_tensor(rng.integers(1, 1_000_000, B))}).to(dev))
+    random_list = torch.as_tensor(rng.permutation(np.arange(1, n_items)).astype(np.int32),
+                                  device=dev)
+    pr = torch.zeros(1, dtype=torch.int64, device=dev)
+    opt = FusedAdam(model.parameters(), lr=1e-3)
+    if ADAM_MODE == 'deferred':
+        opt.enable_deferred(model.deferred_tables())
+    it = [0]
+    gs = None
+    graphed = GRAPH_STEP and model.graph_step_safe      # as the Trainer decides
+    if graphed:
+        from recbole_amd.trainer.graph_step import GraphedTrainStep
+        gs = GraphedTrainStep(model, opt)
+
+    def step():
+        b = batches[it[0] % n_batches]
+        it[0] += 1
+        if not ce:
+            b.interaction['neg_item_id'] = ops.sample_walk(random_list, pr, b['user_id'], 1,
+                                                           None, None, 1_000_000, False)
+        if gs is not None:
+            gs.step(b)
+            return
+        opt.zero_grad()
+        loss_ = model.calculate_loss(b)
+        loss_.backward()
+        opt.step()
+
+    t = _timed(step, steps, warmup, opt)
+    return {
+        'config': 'C3', 'model': 'GRU4Rec',
+        'loss': 'BPR' if not ce else loss, 'metric': 'train sequences/s',
+        'value': round(B / t, 1), 'unit': 'sequences/s', 'ms_per_step': round(t * 1e3, 3),
+        'batch': B, 'steps': steps, 'adam_mode': ADAM_MODE, 'graph_step': graphed,
+        'workload': f'GRU4Rec Amazon-Books-shape: {n_items:,} items (incl. PAD), L={L}, '
+                    f'E={E}, H={H}, 1 layer, dropout 0.3, dense Adam',
+        'dtype': 'fp32', 'data': 'synthetic (Zipf(1.1) items, Poisson(20)+4 lengths, seeded)',
+        'peak_allocated_MB': round(torch.cuda.max_memory_allocated(dev) / 1e6, 1),
+    }
+
+
 def _c3_ce_record(dev, step, opt, model, batches, loss, steps, warmup, n_items, B, L, d):
     """The C3 step with the full-catalogue cross entropy: sequences/s, the peak allocated
     memory of the run (measured before the loss-only timings below), and the loss's own forward / backward call times (HIP
@@ -672,6 +752,8 @@ def main():
     ap.add_argument('--c3-loss', default='SSM', choices=list(C3_LOSSES),
                     help='C3 loss: sampled softmax (default) or the full-catalogue cross '
                          'entropy on the library path / on K12')
+    ap.add_argument('--c3-model', default='SASRec', choices=['SASRec', 'GRU4Rec'],
+                    help='the sequential model of the C3-shaped step')
     args = ap.parse_args()
     global CPU_BASELINE, ADAM_MODE, GRAPH_STEP
     CPU_BASELINE = not args.no_cpu_baseline
@@ -680,7 +762,9 @@ def main():
     dev = torch.device('cuda', 0)
     res = []
     for c in args.configs.split(','):
-        if c == 'C3':
+        if c == 'C3' and args.c3_model == 'GRU4Rec':
+            r = bench_c3_gru4rec(dev, args.steps, args.warmup, args.scale, loss=args.c3_loss)
+        elif c == 'C3':
             r = bench_c3(dev, args.steps, args.warmup, args.scale, loss=args.c3_loss)
         elif c == 'C4':
             r = bench_c4(dev, args.steps, args.warmup, args.scale)
