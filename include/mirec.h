@@ -548,8 +548,9 @@ int mirec_adam_flush_f32(const mirec_adam_table* tables, int32_t n_tables, int32
 /* The same flush (same results) for tables whose rows mostly need nothing (the zero
  * state, or current): each wave owns rows_per_wave[q] (1..64, HOST array per table)
  * consecutive rows of table q and completes those that lag one after another, so the
- * grid has rows / (4 * R) workgroups instead of one per row (the workgroup dispatcher,
- * not the replay, bounds a one-per-row flush of a mostly idle table). d >= 64. */
+ * grid has rows / R one-wave workgroups — rows / (4 * R) four-wave ones once the launch
+ * has more than 2^17 waves — instead of one per row (the workgroup dispatcher, not the
+ * replay, bounds a one-per-row flush of a mostly idle table). d >= 64. */
 int mirec_adam_flush_rows_f32(const mirec_adam_table* tables, int32_t n_tables, int32_t d,
                               const int32_t* rows_per_wave, const float* step_consts_dev,
                               const int32_t* step_base_dev, int32_t step_off, double beta1,

@@ -322,12 +322,25 @@ __global__ __launch_bounds__(kFlushRowThreads) void adam_flush_row_kernel(
 // consecutive rows (R per table, host's choice): lanes 0..R-1 read `last`, one ballot
 // lists the rows that lag (or, at an odd target, are current in p_alt only), and the
 // wave completes them one after another with the one-row-per-wave body above (same
-// replay engine, same results). Blocks of four waves: R = 8 makes the grid 32x smaller.
+// replay engine, same results).
+//
+// Workgroup size (the scan form and the per-row-target form below; host's choice per launch,
+// the kernels take it from blockDim): ONE wave while the launch has at most kScanOneWaveMax
+// waves, else four. The waves of a launch differ widely in work — 0 to R lagging rows each,
+// lags of 1 to a whole chunk — and a CU takes a new workgroup only when a whole workgroup's
+// waves are free (as for the deferred kernel's blocks above), so in four-wave workgroups
+// wave slots idle behind the longest wave: C2's closing masked flush runs 122 -> 101-113 us,
+// its full flush 221 -> 186, the chunk advance 95-101 -> 64-83 as one-wave workgroups, and
+// two-wave workgroups land in between. The price is the dispatch
+// of four times the workgroups (~2-3 per ns): past kScanOneWaveMax (a sparse flush of a
+// table of millions of rows) that would outweigh it, and R = 8 with four waves makes the
+// grid 32x smaller than one workgroup per row.
 //
 // MASKED (mirec_adam_flush_masked_f32, the foreground form): a table with a row bitmap
 // (uint32 words, bit r = row r) takes only the rows whose bit equals `want`; the test is
 // part of `need`, and a row outside the selection is neither loaded (not even its
 // `last`: another launch may be completing it) nor marked.
+constexpr int64_t kScanOneWaveMax = 1 << 17;
 struct FlushRows {
   int32_t r[kMaxTables];
 };
@@ -350,7 +363,7 @@ __global__ __launch_bounds__(kAdamThreads) void adam_flush_scan_kernel(
   const int R = rows_per_wave.r[si];
   const int lane = threadIdx.x & 63;
   const int64_t r0 =
-      (((int64_t)blockIdx.x - tabs.block_start[si]) * (kAdamThreads / 64) + (threadIdx.x >> 6)) * R;
+      (((int64_t)blockIdx.x - tabs.block_start[si]) * (blockDim.x >> 6) + (threadIdx.x >> 6)) * R;
   if (r0 >= T.n_rows) return;                          // wave-uniform
   const int target = step_base[0] + step_off;
   int raw = kZeroState;
@@ -385,7 +398,7 @@ __global__ __launch_bounds__(kAdamThreads) void adam_flush_first_kernel(
   const int R = rows_per_wave.r[si];
   const int lane = threadIdx.x & 63;
   const int64_t r0 =
-      (((int64_t)blockIdx.x - tabs.block_start[si]) * (kAdamThreads / 64) + (threadIdx.x >> 6)) * R;
+      (((int64_t)blockIdx.x - tabs.block_start[si]) * (blockDim.x >> 6) + (threadIdx.x >> 6)) * R;
   if (r0 >= T.n_rows) return;                          // wave-uniform
   const int base = step_base[0] + step_off;
   int raw = kZeroState, target = 0;
@@ -514,6 +527,14 @@ int launch_adam(Sched sched, const mirec_adam_table* tables, int32_t n_tables,
   FlushFirst ff;
   memset(&ff, 0, sizeof(ff));
   if (firsts) ff = *firsts;
+  // scan and per-row-target forms: one-wave workgroups while the launch is small enough
+  int scan_threads = kAdamThreads;
+  if (scan && !walk) {
+    int64_t waves = 0;
+    for (int q = 0; q < n_tables; ++q)
+      if (tables[q].n_rows > 0) waves += (tables[q].n_rows + fr.r[q] - 1) / fr.r[q];
+    if (waves <= kScanOneWaveMax) scan_threads = 64;
+  }
   AdamTables tabs;
   memset(&tabs, 0, sizeof(tabs));
   const bool deferred = sched == Sched::kDeferred;
@@ -565,7 +586,7 @@ int launch_adam(Sched sched, const mirec_adam_table* tables, int32_t n_tables,
     } else {
       tabs.block_start[q] = blocks;
       const int64_t rows_per_block =
-          scan ? (int64_t)(kAdamThreads / 64) * fr.r[q]
+          scan ? (int64_t)(scan_threads / 64) * fr.r[q]
           : (sched == Sched::kFlush && d >= 64) ? kFlushRowThreads / 64
           : sched == Sched::kFlush ? kFlushRows
                                    : kAdamRows;
@@ -605,14 +626,17 @@ int launch_adam(Sched sched, const mirec_adam_table* tables, int32_t n_tables,
       hipLaunchKernelGGL(adam_flush_walk_kernel<(DD >= 64 ? DD : 64)>, grd, dim3(64), 0, st,   \
                          tabs, consts, step_base, step_off, k, fm);                          \
     else if (DD >= 64 && scan && firsts)                                                     \
-      hipLaunchKernelGGL(adam_flush_first_kernel<(DD >= 64 ? DD : 64)>, grd, blk, 0, st, tabs, \
-                         consts, step_base, step_off, k, fr, ff);                            \
+      hipLaunchKernelGGL(adam_flush_first_kernel<(DD >= 64 ? DD : 64)>, grd,                 \
+                         dim3(scan_threads), 0, st, tabs, consts, step_base, step_off, k,    \
+                         fr, ff);                                                            \
     else if (DD >= 64 && scan && masks)                                                      \
-      hipLaunchKernelGGL((adam_flush_scan_kernel<(DD >= 64 ? DD : 64), true>), grd, blk, 0,    \
-                         st, tabs, consts, step_base, step_off, k, fr, fm);                  \
+      hipLaunchKernelGGL((adam_flush_scan_kernel<(DD >= 64 ? DD : 64), true>), grd,          \
+                         dim3(scan_threads), 0, st, tabs, consts, step_base, step_off, k,    \
+                         fr, fm);                                                            \
     else if (DD >= 64 && scan)                                                               \
-      hipLaunchKernelGGL((adam_flush_scan_kernel<(DD >= 64 ? DD : 64), false>), grd, blk, 0,   \
-                         st, tabs, consts, step_base, step_off, k, fr, fm);                  \
+      hipLaunchKernelGGL((adam_flush_scan_kernel<(DD >= 64 ? DD : 64), false>), grd,         \
+                         dim3(scan_threads), 0, st, tabs, consts, step_base, step_off, k,    \
+                         fr, fm);                                                            \
     else if (DD >= 64)                                                                       \
       hipLaunchKernelGGL(adam_flush_row_kernel<(DD >= 64 ? DD : 64)>, grd,                   \
                          dim3(kFlushRowThreads), 0, st, tabs,                                \

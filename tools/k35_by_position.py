@@ -5,7 +5,8 @@ flushes (adam_flush_scan_kernel / adam_flush_row_kernel); per chunk: launches, s
 first launch's start to the last one's end, the sum of the durations, the mean duration;
 for the steady 64-step chunks each launch's duration at positions 0-7, 28-35 and 56-63;
 and the closing flushes (FG), the background flushes (BG: adam_flush_walk_kernel) and the
-advance launches (ADV: adam_flush_first_kernel) in time order.
+advance launches (ADV: adam_flush_first_kernel) in time order, each foreground launch with the
+gap since the previous foreground launch of the list ended.
 
 usage: python tools/k35_by_position.py <trace dir> [label]
 """
@@ -69,9 +70,13 @@ def main(src, label=''):
         d = np.array([us(e - s) for s, e in c]).reshape(8, 8).mean(axis=1)
         print(f'chunk {i}: ' + ' '.join(f'{x:6.2f}' for x in d))
     print('## flush launches')
+    prev = None
     for kind, s, e in flushes:
         if s >= t0:
-            print(f'{kind:3s} t={us(s - t0):9.1f} dur={us(e - s):7.1f}')
+            gap = f'  gap={us(s - prev):6.1f}' if prev is not None and kind != 'BG' else ''
+            print(f'{kind:3s} t={us(s - t0):9.1f} dur={us(e - s):7.1f}{gap}')
+            if kind != 'BG':
+                prev = e
 
 
 if __name__ == '__main__':
