@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define MIREC_ABI_VERSION 20
+#define MIREC_ABI_VERSION 21
 
 int mirec_abi_version(void);
 const char* mirec_last_error(void);
@@ -1252,6 +1252,62 @@ int mirec_alltoallv_rows_f32(mirec_comm* comm, const float* send, const int64_t*
 /* buf[n] <- the sum of every rank's buf, added in rank order (the same bits on every
  * rank); n <= wcap*d, a multiple of 4, buf 16-B aligned. Entry / exit barriers included. */
 int mirec_allreduce_sum_f32(mirec_comm* comm, float* buf, int64_t n, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * K14  NeuMF (recbole/model/general_recommender/neumf.py):
+ *   logit(u, i) = w_mf . (U_mf[u] * I_mf[i]) + w_h . MLP([U_mlp[u] | I_mlp[i]]) + b.
+ *
+ * K14a mirec_neumf_gather_f32: one launch for a batch of (user, item) ids (device int64):
+ *   x [B, 2 dm] = [U_mlp[u] | I_mlp[i]] (x NULL: the MLP half is off) and
+ *   z_mf [B] = sum_k w_mf[k] U_mf[u, k] I_mf[i, k] (U_mf NULL: zeros). Widths are
+ *   multiples of 4, dmf <= 256; an id outside its table reads a zero row.
+ * K14b mirec_neumf_gather_bwd_f32: from g [B] (dloss/dlogit) and gx [B, 2 dm], one launch
+ *   writes the per-row gradients gU_mf = g w_mf * I_mf[i], gI_mf = g w_mf * U_mf[u]
+ *   ([B, dmf]), the halves of gx as gU_mlp / gI_mlp ([B, dm]) and
+ *   dw_mf [dmf] = sum_b g_b U_mf[u_b] * I_mf[i_b], summed in a fixed order by one block (no
+ *   float atomics). gU_mf NULL / gx NULL: that half is skipped.
+ * mirec_neumf_project_f32: out [n, H] = bias + T[rows] W[:, col0 : col0 + dm]^T with
+ *   rows = idx (device int64) or 0..n-1 (idx NULL), W [H, ldw] row-major: the user part A
+ *   and the item part Bm of the first MLP layer.
+ * K14c mirec_pair_mlp_f32: the fused pair-MLP full-sort scorer. With A [nq, H[0]] (bias
+ *   included) and Bm [I, H[0]]: h1 = relu(A[u] + Bm[i]); layers 2..L (W[l] [H[l], H[l-1]]
+ *   row-major, b[l], ReLU) on fp32 MFMA; logit = w_h . h_L + Pq[u] . I_mf[i] + bias[0]
+ *   (Pq [nq, dmf] = U_mf[u] * w_mf; dmf 0: no MF term; bias: a device scalar or NULL).
+ *   scores NULL: item 0 and the history items (hist_ptr / hist_cols, sorted CSR as K6) are
+ *   masked and the K best logits per user come back as mirec_fullsort_topk_f32's outputs,
+ *   ties by (score desc, item id asc). scores non-NULL: the [nq, I] logits, no mask, no
+ *   top-K. 2..4 hidden layers, widths multiples of 16 in 16..256, dmf a multiple of 4 up
+ *   to 128, K <= 50. mirec_pair_mlp_supported: 1 when a descriptor's shapes are taken.
+ */
+typedef struct mirec_pair_mlp {
+  int32_t n_hidden;         /* hidden layers L */
+  int32_t H[4];             /* their widths */
+  int32_t dmf;              /* MF width, 0 = off */
+  int32_t pad_;
+  const float* W[4];        /* W[l], l = 1..L-1 (W[0], the first layer, is in A / Bm) */
+  const float* b[4];        /* b[l], l = 1..L-1, or NULL */
+  const float* w_h;         /* [H[L-1]] */
+  const float* bias;        /* device scalar or NULL */
+} mirec_pair_mlp;
+
+int mirec_neumf_gather_f32(const int64_t* user, const int64_t* item, int64_t B,
+                           const float* U_mf, const float* I_mf, int32_t dmf, const float* w_mf,
+                           const float* U_mlp, const float* I_mlp, int32_t dm, int64_t n_users,
+                           int64_t n_items, float* x, float* z_mf, void* stream);
+int mirec_neumf_gather_bwd_f32(const int64_t* user, const int64_t* item, int64_t B,
+                               const float* U_mf, const float* I_mf, int32_t dmf,
+                               const float* w_mf, const float* g, const float* gx, int32_t dm,
+                               int64_t n_users, int64_t n_items, float* gU_mf, float* gI_mf,
+                               float* gU_mlp, float* gI_mlp, float* dw_mf, void* stream);
+int mirec_neumf_project_f32(const float* T, const int64_t* idx, int64_t n, int64_t n_rows,
+                            int32_t dm, const float* W, int32_t ldw, int32_t col0,
+                            const float* bias, int32_t H, float* out, void* stream);
+int mirec_pair_mlp_supported(const mirec_pair_mlp* mlp);
+int mirec_pair_mlp_f32(const mirec_pair_mlp* mlp, const float* A, const float* Pq, int64_t nq,
+                       const float* Bm, const float* I_mf, int64_t I, const int64_t* hist_ptr,
+                       const int32_t* hist_cols, const int64_t* pos_ptr, const int32_t* pos_cols,
+                       int32_t K, float* top_scores, int32_t* top_ids, uint8_t* pos_flags,
+                       float* scores, void* stream);
 
 #ifdef __cplusplus
 }

@@ -56,6 +56,12 @@ class MlpDesc(ctypes.Structure):
                 ('wcount', _P)]
 
 
+class PairMlpDesc(ctypes.Structure):
+    """struct mirec_pair_mlp (include/mirec.h, K14c)."""
+    _fields_ = [('n_hidden', c_int32), ('H', c_int32 * 4), ('dmf', c_int32), ('pad_', c_int32),
+                ('W', _P * 4), ('b', _P * 4), ('w_h', _P), ('bias', _P)]
+
+
 class FlatParam(ctypes.Structure):
     """struct mirec_flat_param (include/mirec.h)."""
     _fields_ = [('p', _P), ('m', _P), ('v', _P), ('g', _P), ('n', c_int64)]
@@ -296,9 +302,18 @@ SIGNATURES = {
                                       _P]),
     "mirec_gather_sqnorm_f32": (c_int, [_P, c_int64, c_int32, _P, c_int64, _P, _P]),
     "mirec_gather_scale_rows_f32": (c_int, [_P, c_int64, c_int32, _P, c_int64, _P, _P, _P]),
+    "mirec_neumf_gather_f32": (c_int, [_P, _P, c_int64, _P, _P, c_int32, _P, _P, _P, c_int32,
+                                       c_int64, c_int64, _P, _P, _P]),
+    "mirec_neumf_gather_bwd_f32": (c_int, [_P, _P, c_int64, _P, _P, c_int32, _P, _P, _P, c_int32,
+                                           c_int64, c_int64, _P, _P, _P, _P, _P, _P]),
+    "mirec_neumf_project_f32": (c_int, [_P, _P, c_int64, c_int64, c_int32, _P, c_int32, c_int32,
+                                        _P, c_int32, _P, _P]),
+    "mirec_pair_mlp_supported": (c_int, [_P]),
+    "mirec_pair_mlp_f32": (c_int, [_P, _P, _P, c_int64, _P, _P, c_int64, _P, _P, _P, _P, c_int32,
+                                   _P, _P, _P, _P, _P]),
 }
 
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 
 class NativeError(RuntimeError):

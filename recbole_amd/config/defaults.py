@@ -1,6 +1,6 @@
 """Default configuration values, restated as Python data from the reference's
 property files (recbole/properties/overall.yaml, dataset/sample.yaml,
-dataset/ml-100k.yaml, model/{BPR,LightGCN,SASRec,GRU4Rec,DeepFM}.yaml,
+dataset/ml-100k.yaml, model/{BPR,LightGCN,SASRec,GRU4Rec,DeepFM,NeuMF}.yaml,
 quick_start_config/{sequential,context-aware}.yaml)."""
 from recbole_amd.utils.enum_type import ModelType
 
@@ -62,6 +62,10 @@ MODEL_DEFAULTS = {
     'GRU4Rec': dict(embedding_size=64, hidden_size=128, num_layers=1, dropout_prob=0.3,
                     loss_type='CE'),
     'DeepFM': dict(embedding_size=10, mlp_hidden_size=[128, 128, 128], dropout_prob=0.2),
+    'NeuMF': dict(mf_embedding_size=64, mlp_embedding_size=64, mlp_hidden_size=[128, 64, 32],
+                  dropout_prob=0.0, weight_decay=1e-08, mf_train=True, mlp_train=True,
+                  valid_metric='HIT@10', use_pretrain=False, mf_pretrain_path=None,
+                  mlp_pretrain_path=None),
 }
 
 # quick_start_config/context-aware_ml-100k.yaml, applied after the type preset

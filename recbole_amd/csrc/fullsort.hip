@@ -26,50 +26,13 @@
 // is permuted (k = 4*(s>>1) + 2h + (s&1)) so both operands load as float2; the
 // MFMA result is an exact-f32 fma chain in that order.
 #include "common.h"
+#include "topk.h"   // topk_insert / topk_merge_insert, hist_lower_bound
 
 namespace mirec {
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 constexpr int kFsThreads = 256;
-
-// Sorted insert into a best-first register list, branch-free (v_cndmask only;
-// bitwise |/& on the predicates so clang emits no exec-mask branches).
-// Scan form: strict '>' — each lane visits its items in increasing id order,
-// so an equal score arriving later (higher id) correctly ranks after.
-template <int KC>
-__device__ __forceinline__ void topk_insert(float (&ts)[KC], int (&ti)[KC], float v, int id) {
-#pragma unroll
-  for (int t = KC - 1; t > 0; --t) {
-    const bool up = v > ts[t - 1];
-    const bool here = v > ts[t];
-    const float ns = up ? ts[t - 1] : (here ? v : ts[t]);
-    const int ni = up ? ti[t - 1] : (here ? id : ti[t]);
-    ts[t] = ns;
-    ti[t] = ni;
-  }
-  const bool h0 = v > ts[0];
-  ts[0] = h0 ? v : ts[0];
-  ti[0] = h0 ? id : ti[0];
-}
-
-// Merge form: full order (score desc, id asc) for combining two lanes' lists.
-template <int KC>
-__device__ __forceinline__ void topk_merge_insert(float (&ts)[KC], int (&ti)[KC], float v,
-                                                  int id) {
-#pragma unroll
-  for (int t = KC - 1; t > 0; --t) {
-    const bool up = (v > ts[t - 1]) | ((v == ts[t - 1]) & (id < ti[t - 1]));
-    const bool here = (v > ts[t]) | ((v == ts[t]) & (id < ti[t]));
-    const float ns = up ? ts[t - 1] : (here ? v : ts[t]);
-    const int ni = up ? ti[t - 1] : (here ? id : ti[t]);
-    ts[t] = ns;
-    ti[t] = ni;
-  }
-  const bool h0 = (v > ts[0]) | ((v == ts[0]) & (id < ti[0]));
-  ts[0] = h0 ? v : ts[0];
-  ti[0] = h0 ? id : ti[0];
-}
 
 // Stage items [base, base+32) of EI into LDS rows of LDR floats (zero past I).
 template <int D>
@@ -161,14 +124,8 @@ __global__ __launch_bounds__(kFsThreads, MIREC_FS_WAVES_PER_EU(D)) void fullsort
   if (threadIdx.x < 128 && qu < nq && hist_ptr) {
     hcur = hist_ptr[qu];
     hend = hist_ptr[qu + 1];
-    if (ilo > 0) {                          // sorted: lower_bound of the split's first item
-      int64_t a = hcur, b = hend;
-      while (a < b) {
-        const int64_t mid = (a + b) >> 1;
-        if (hist_cols[mid] < ilo) a = mid + 1; else b = mid;
-      }
-      hcur = a;
-    }
+    // sorted: lower_bound of the split's first item
+    if (ilo > 0) hcur = hist_lower_bound(hist_cols, hcur, hend, ilo);
     if (hcur < hend) hnext = hist_cols[hcur];
   }
   auto build_mask = [&](int64_t base, uint32_t (*dst)[128]) {

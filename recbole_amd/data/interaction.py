@@ -102,8 +102,10 @@ class Interaction(object):
 
     def repeat_interleave(self, repeats, dim=0):
         ret = {k: t.repeat_interleave(repeats, dim=dim) for k, t in self.interaction.items()}
-        npl = list(np.multiply(self.pos_len_list, repeats)) if self.pos_len_list else None
-        nul = list(np.multiply(self.user_len_list, repeats)) if self.user_len_list else None
+        # the loaders hand the length lists over as numpy arrays: no truth value of an array
+        given = lambda x: x is not None and len(x) > 0
+        npl = list(np.multiply(self.pos_len_list, repeats)) if given(self.pos_len_list) else None
+        nul = list(np.multiply(self.user_len_list, repeats)) if given(self.user_len_list) else None
         return Interaction(ret, npl, nul)
 
     def update(self, new_inter):

@@ -186,6 +186,38 @@ def fused_deep(mlp_layers, predict, x):
     return _DeepFn.apply(mlp_layers, len(lins), x, *params)
 
 
+def tensors_supported(mlp_layers, weights, x) -> bool:
+    """fused_supported for explicit weights (the hidden Linears' followed by the head's)."""
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 2):
+        return False
+    if getattr(mlp_layers, 'use_bn', False) or len(weights) > MLP_MAX_LAYERS:
+        return False
+    act = getattr(mlp_layers, 'activation', 'relu')
+    if not (isinstance(act, str) and act.lower() == 'relu'):
+        return False
+    dims = [weights[0].shape[1]] + [w.shape[0] for w in weights]
+    if any(d < 1 or d > 1024 for d in dims) or any(d % 4 for d in dims[:-1]):
+        return False
+    if dims[0] != x.shape[1] or any(w.shape[1] != k for w, k in zip(weights, dims[:-1])):
+        return False
+    pad = lambda w: (w + 15) // 16 * 16 + 4
+    if 16 * 4 * (pad(max(dims[0::2])) + pad(max(dims[1::2]))) > 65536:
+        return False
+    return all(w.is_cuda and w.dtype == torch.float32 and w.is_contiguous()
+               and w.data_ptr() % 16 == 0 for w in weights)
+
+
+def fused_deep_tensors(mlp_layers, x, weights, biases):
+    """fused_deep with the layers given as tensors: weights[l] [out_l, in_l] and biases[l]
+    ([out_l] or None) for the hidden layers followed by the head. The head may be a column
+    slice of a wider Linear's weight (NeuMF's predict_layer): autograd carries its gradient
+    back into the slice. mlp_layers gives the dropout rate, the mode and the K10 state."""
+    params = []
+    for w, b in zip(weights, biases):
+        params += [w, b]
+    return _DeepFn.apply(mlp_layers, len(weights), x, *params)
+
+
 def deep_forward(mlp_layers, predict, x):
     """K10 where it applies, the modules' torch path otherwise."""
     if fused_supported(mlp_layers, predict, x):

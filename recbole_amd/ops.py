@@ -1004,6 +1004,147 @@ def score_matrix(Uq, EI, out=None):
     return out
 
 
+# ---------------------------------------------------------------- K14 NeuMF
+def neumf_gather(user, item, U_mf, I_mf, w_mf, U_mlp, I_mlp):
+    """K14a: x [B, 2 dm] = [U_mlp[u] | I_mlp[i]] (None when the MLP tables are None) and
+    z_mf [B] = sum_k w_mf[k] U_mf[u, k] I_mf[i, k] (zeros when the MF tables are None)."""
+    user, item = _dev(user, torch.int64, "user"), _dev(item, torch.int64, "item")
+    B, dev = user.numel(), user.device
+    mf, mlp = U_mf is not None, U_mlp is not None
+    n_users = (U_mf if mf else U_mlp).shape[0]
+    n_items = (I_mf if mf else I_mlp).shape[0]
+    for n_, t_ in (("U_mf", U_mf), ("I_mf", I_mf), ("w_mf", w_mf), ("U_mlp", U_mlp),
+                   ("I_mlp", I_mlp)):
+        if t_ is not None:
+            _dev(t_, torch.float32, n_)
+    dmf = U_mf.shape[1] if mf else 0
+    dm = U_mlp.shape[1] if mlp else 0
+    x = torch.empty(B, 2 * dm, dtype=torch.float32, device=dev) if mlp else None
+    z = torch.empty(B, dtype=torch.float32, device=dev)
+    with timed_launch('neumf_gather'):
+        rc = lib().mirec_neumf_gather_f32(ptr(user), ptr(item), B, ptr(U_mf), ptr(I_mf), dmf,
+                                          ptr(w_mf), ptr(U_mlp), ptr(I_mlp), dm, n_users,
+                                          n_items, ptr(x), ptr(z), stream_handle())
+    check(rc, "mirec_neumf_gather_f32")
+    return x, z
+
+
+def neumf_gather_bwd(user, item, U_mf, I_mf, w_mf, g, gx, n_users: int, n_items: int):
+    """K14b: per-row gradients (gU_mf, gI_mf, gU_mlp, gI_mlp) and dw_mf; g None skips the
+    MF half, gx None the MLP half."""
+    B, dev = user.numel(), user.device
+    mf, mlp = g is not None, gx is not None
+    E = lambda *sh: torch.empty(*sh, dtype=torch.float32, device=dev)
+    dmf = U_mf.shape[1] if mf else 0
+    dm = gx.shape[1] // 2 if mlp else 0
+    gU_mf, gI_mf, dw = (E(B, dmf), E(B, dmf), E(dmf)) if mf else (None, None, None)
+    gU_mlp, gI_mlp = (E(B, dm), E(B, dm)) if mlp else (None, None)
+    if mf:
+        g = _dev(g, torch.float32, "g")
+    if mlp:
+        gx = _dev(gx, torch.float32, "gx")
+    with timed_launch('neumf_gather_bwd'):
+        rc = lib().mirec_neumf_gather_bwd_f32(
+            ptr(user), ptr(item), B, ptr(U_mf) if mf else None, ptr(I_mf) if mf else None, dmf,
+            ptr(w_mf) if mf else None, ptr(g), ptr(gx), dm, n_users, n_items, ptr(gU_mf),
+            ptr(gI_mf), ptr(gU_mlp), ptr(gI_mlp), ptr(dw), stream_handle())
+    check(rc, "mirec_neumf_gather_bwd_f32")
+    return gU_mf, gI_mf, gU_mlp, gI_mlp, dw
+
+
+def neumf_project(table, W, col0: int, bias=None, idx=None):
+    """out [n, H] = bias + table[rows] @ W[:, col0:col0 + dm].T (rows = idx, or every row):
+    the user part A / item part Bm of the first MLP layer for K14c."""
+    _dev(table, torch.float32, "table")
+    _dev(W, torch.float32, "W")
+    n = table.shape[0] if idx is None else idx.numel()
+    if idx is not None:
+        idx = _dev(idx, torch.int64, "idx")
+    out = torch.empty(n, W.shape[0], dtype=torch.float32, device=table.device)
+    rc = lib().mirec_neumf_project_f32(ptr(table), ptr(idx), n, table.shape[0], table.shape[1],
+                                       ptr(W), W.shape[1], col0, ptr(bias), W.shape[0], ptr(out),
+                                       stream_handle())
+    check(rc, "mirec_neumf_project_f32")
+    return out
+
+
+def pair_mlp_desc(weights, biases, w_h, bias, dmf: int):
+    """struct mirec_pair_mlp for hidden layers 2..L (weights[l] [H_l, H_{l-1}], l >= 1;
+    weights[0] only gives H_1) and the head (w_h [H_L], bias: a 1-element tensor or None).
+    Returns (descriptor, tensors it points at)."""
+    from recbole_amd._native import PairMlpDesc
+    d = PairMlpDesc()
+    d.n_hidden = len(weights)
+    keep = []
+    for l, w in enumerate(weights[:4]):
+        d.H[l] = w.shape[0]
+        if l >= 1:
+            w = _dev(w, torch.float32, "weight")
+            d.W[l] = ptr(w)
+            d.b[l] = ptr(biases[l])
+            keep += [w, biases[l]]
+    d.dmf = dmf
+    d.w_h, d.bias = ptr(w_h), ptr(bias)
+    keep += [w_h, bias]
+    return d, keep
+
+
+def pair_mlp_supported(widths, dmf: int) -> bool:
+    """K14c's shapes: 2..4 hidden layers of widths that are multiples of 16 in 16..256,
+    dmf a multiple of 4 up to 128 (0: no MF term), and an LDS layout that fits."""
+    from recbole_amd._native import PairMlpDesc
+    if not 2 <= len(widths) <= 4:
+        return False
+    d = PairMlpDesc()
+    d.n_hidden = len(widths)
+    for l, h in enumerate(widths):
+        d.H[l] = h
+    d.dmf = dmf
+    for l in range(1, len(widths)):            # non-NULL, aligned: shapes only are judged
+        d.W[l] = 16
+    d.w_h = 16
+    return lib().mirec_pair_mlp_supported(ctypes.byref(d)) == 1
+
+
+def pair_mlp_topk(desc, A, Pq, Bm, I_mf, K: int, hist_ptr=None, hist_cols=None, pos_ptr=None,
+                  pos_cols=None, out: dict | None = None) -> dict:
+    """K14c, top-K mode: fullsort_topk's outputs ('scores' = logits, 'ids', 'pos_flags')."""
+    _dev(A, torch.float32, "A")
+    _dev(Bm, torch.float32, "Bm")
+    for n_, t_, dt in (("hist_ptr", hist_ptr, torch.int64), ("hist_cols", hist_cols, torch.int32),
+                       ("pos_ptr", pos_ptr, torch.int64), ("pos_cols", pos_cols, torch.int32),
+                       ("Pq", Pq, torch.float32), ("I_mf", I_mf, torch.float32)):
+        if t_ is not None:
+            _dev(t_, dt, n_)
+    nq, dev = A.shape[0], A.device
+    o = {} if out is None else out
+    o.setdefault("scores", torch.empty(nq, K, dtype=torch.float32, device=dev))
+    o.setdefault("ids", torch.empty(nq, K, dtype=torch.int32, device=dev))
+    if pos_ptr is not None:
+        o.setdefault("pos_flags", torch.empty(nq, K, dtype=torch.uint8, device=dev))
+    with timed_launch('pair_mlp'):
+        rc = lib().mirec_pair_mlp_f32(ctypes.byref(desc), ptr(A), ptr(Pq), nq, ptr(Bm), ptr(I_mf),
+                                      Bm.shape[0], ptr(hist_ptr), ptr(hist_cols), ptr(pos_ptr),
+                                      ptr(pos_cols), K, ptr(o["scores"]), ptr(o["ids"]),
+                                      ptr(o.get("pos_flags")), None, stream_handle())
+    check(rc, "mirec_pair_mlp_f32")
+    return o
+
+
+def pair_mlp_scores(desc, A, Pq, Bm, I_mf, out=None):
+    """K14c, scores mode: the [nq, I] logits (no mask, no top-K)."""
+    _dev(A, torch.float32, "A")
+    _dev(Bm, torch.float32, "Bm")
+    if out is None:
+        out = torch.empty(A.shape[0], Bm.shape[0], dtype=torch.float32, device=A.device)
+    with timed_launch('pair_mlp'):
+        rc = lib().mirec_pair_mlp_f32(ctypes.byref(desc), ptr(A), ptr(Pq), A.shape[0], ptr(Bm),
+                                      ptr(I_mf), Bm.shape[0], None, None, None, None, 1, None,
+                                      None, None, ptr(out), stream_handle())
+    check(rc, "mirec_pair_mlp_f32")
+    return out
+
+
 # ---------------------------------------------------------------- K12 full-catalogue CE
 def full_ce_splits(B: int, I: int, d: int, splits: int = 0) -> int:
     """The item split K12 uses for `splits` (0 = auto): a host-side pure function."""

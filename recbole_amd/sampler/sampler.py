@@ -175,6 +175,8 @@ class AbstractSampler(object):
         """sampler.py:103-154 (both branches), on the device."""
         if self.random_list_length == 0:
             raise ValueError('the random list is empty; nothing to sample from')
+        if self._rl_dev is None and self.device is None and not torch.cuda.is_available():
+            return self._host_walk(key_ids, num)      # a machine without a GPU (use_gpu: False)
         if self._rl_dev is None:
             self.to_device(self._default_device())
         keys = torch.as_tensor(key_ids)
@@ -193,6 +195,55 @@ class AbstractSampler(object):
                               n_bits=n_bits)
         self.check_status()
         return out
+
+    def _host_walk(self, key_ids, num):
+        """K4's walk (include/mirec.h) in numpy, for a machine with no GPU at all (a CPU
+        run asked for with use_gpu: False; never taken where a GPU exists): slot t of round
+        0 takes random_list[(pr + t) mod L], out[j * Kb + k] being the j-th value of key k;
+        every slot whose value is in the key's used set is refilled, in ascending slot
+        order, from the continuing walk until none is left. Returns a CPU int64 tensor."""
+        if self.alias is not None:
+            raise RuntimeError('alias negative sampling runs on the GPU only')
+        keys = np.atleast_1d(np.asarray(torch.as_tensor(key_ids).cpu().numpy(), dtype=np.int64))
+        if len(keys) and (keys.min() < 0 or keys.max() >= self.n_users):
+            raise ValueError('user_id out of range in negative sampling')
+        L, rl = self.random_list_length, np.asarray(self.random_list, dtype=np.int64)
+        n, pr = len(keys) * int(num), int(self._pr_host)
+        out = rl[(pr + np.arange(n)) % L]
+        pr += n
+        csr = self._used_host()
+        if csr is not None and n:
+            # every (key, used item) pair as one code, ascending (rows in key order, each
+            # row sorted): membership by binary search
+            cache = self.__dict__.setdefault('_host_codes', {})
+            if self.phase not in cache:
+                ptr, cols = csr
+                cache[self.phase] = np.repeat(np.arange(self.n_users, dtype=np.int64),
+                                              np.diff(ptr)) * self.n_items \
+                    + np.asarray(cols, dtype=np.int64)
+            codes = cache[self.phase]
+            slot_keys = np.tile(keys, int(num))
+
+            def used(s):
+                q = slot_keys[s] * self.n_items + out[s]
+                at = np.minimum(np.searchsorted(codes, q), max(len(codes) - 1, 0))
+                return codes[at] == q if len(codes) else np.zeros(len(q), dtype=bool)
+            bad = np.flatnonzero(used(np.arange(n)))
+            rounds = 0
+            while len(bad):
+                out[bad] = rl[(pr + np.arange(len(bad))) % L]
+                pr += len(bad)
+                bad = bad[used(bad)]
+                rounds += 1
+                if rounds > 4 * L + 1024:
+                    raise RuntimeError('negative sampling did not terminate: a user has no free '
+                                       'item the walk over random_list can reach')
+        self._pr_host = pr % L
+        return torch.as_tensor(out, dtype=torch.int64)
+
+    def _used_host(self):
+        """(ptr, cols) of the phase's used sets on the host, or None (no rejection)."""
+        return None
 
     def launch_batches(self, keys_dev, batch_keys, n_batches, num, out, out_stride=0, ws=None):
         """Walk `n_batches` consecutive batches in ONE kernel launch (the trainer's
@@ -351,6 +402,11 @@ class Sampler(AbstractSampler):
         if self._pr_dev is not None:
             new._pr_dev = self._pr_dev.clone()
         return new
+
+    def _used_host(self):
+        if self.phase is None:
+            raise ValueError('call set_phase() before sampling')
+        return self.used_csr[self.phase]
 
     def _used_dev(self):
         if self.phase is None:

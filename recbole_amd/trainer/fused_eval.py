@@ -39,6 +39,26 @@ def fused_full_sort_eval(model, eval_data, topk_evaluator, user_batch=1 << 20, d
     return topk_evaluator.evaluate_pos_idx(pos_idx, eval_data.get_pos_len_list())
 
 
+def fused_pair_full_sort_eval(model, eval_data, topk_evaluator, user_batch=1 << 16):
+    """Trainer.evaluate for a FULL loader and a model whose score is not a dot product but a
+    per-pair MLP (NeuMF): model.fused_pair_scorer() forms the item part of the first layer
+    once, then per user batch the user part and K14c — the layers 2..L, the MF dot, the
+    pad / history mask, the top-K and the positive flags in one kernel. One GPU."""
+    scorer = model.fused_pair_scorer()
+    dev = scorer.device
+    K = max(topk_evaluator.topk)
+    uids, hist_ptr, hist_cols, pos_ptr, pos_cols = eval_data.device_csr(dev)
+    n = uids.numel()
+    flags = torch.empty(n, K, dtype=torch.uint8, device=dev)
+    for s in range(0, n, user_batch):
+        e = min(n, s + user_batch)
+        scorer.topk(uids[s:e], K, hist_ptr=hist_ptr[s:e + 1], hist_cols=hist_cols,
+                    pos_ptr=pos_ptr[s:e + 1], pos_cols=pos_cols,
+                    out={'pos_flags': flags[s:e]})
+    pos_idx = flags.cpu().numpy().astype(bool)
+    return topk_evaluator.evaluate_pos_idx(pos_idx, eval_data.get_pos_len_list())
+
+
 def _fullsort_round_users(dev, d):
     """Users of one full round of K6 workgroups (128 users each; two resident per
     CU for d <= 128, one for d = 256): launches of this size fill the chip."""

@@ -12,8 +12,9 @@ checkpoint dict as the reference. Two execution paths:
   kernels inside calculate_loss and FusedAdam (or torch's learners) as step.
 
 Evaluation of a FULL loader uses the fused K6 scorer when the model provides
-fused_user_vectors()/fused_item_table(); otherwise the reference's
-full_sort_predict + mask + swap + TopKEvaluator.collect sequence.
+fused_user_vectors()/fused_item_table(), the fused pair-MLP scorer (K14c) when it
+provides fused_pair_scorer(); otherwise the reference's full_sort_predict + mask +
+swap + TopKEvaluator.collect sequence.
 
 Documented difference: the NaN check of the fused path runs once per epoch
 (the reference checks every batch, trainer.py:169, at the cost of a host sync
@@ -36,7 +37,8 @@ from recbole_amd.data.dataloader.sequential_dataloader import SequentialNegSampl
 from recbole_amd.sampler import RepeatableSampler
 from recbole_amd.trainer.fused import FusedBPRTrainStep
 from recbole_amd.trainer.fused_eval import (fused_full_sort_eval, fused_general_sampled_eval,
-                                            fused_seq_full_sort_eval, fused_seq_sampled_eval)
+                                            fused_pair_full_sort_eval, fused_seq_full_sort_eval,
+                                            fused_seq_sampled_eval)
 from recbole_amd.trainer.sharded import ShardedBPRTrainStep
 from recbole_amd.trainer.dist import DataParallelStep, active_group
 from recbole_amd.trainer.optim import FusedAdam
@@ -107,6 +109,10 @@ class Trainer(AbstractTrainer):
         """trainer.py:109-130; 'adam' runs on the K5 kernel (FusedAdam)."""
         name = self.learner.lower()
         if name == 'adam':
+            params = list(params)
+            if params and not params[0].is_cuda:
+                # a CPU model (use_gpu: False): K5 needs the GPU, torch's Adam is the reference's
+                return optim.Adam(params, lr=self.learning_rate, weight_decay=self.weight_decay)
             return FusedAdam(params, lr=self.learning_rate, weight_decay=self.weight_decay)
         if name == 'sgd':
             return optim.SGD(params, lr=self.learning_rate, weight_decay=self.weight_decay)
@@ -380,6 +386,12 @@ class Trainer(AbstractTrainer):
                 and hasattr(self.model, 'fused_user_vectors')
                 and self.model.fused_item_table().is_cuda):
             return fused_general_sampled_eval(self.model, eval_data, self.evaluator)
+        if (eval_data.dl_type == DataLoaderType.FULL and self.config['fused_eval'] is not False
+                and hasattr(self.model, 'fused_pair_scorer') and self._dp is None
+                and topk is not None and len(self.evaluator.evaluators) == 1
+                and max(topk.topk) <= 50 and self.model.pair_scorer_applies()):
+            # a per-pair MLP score (NeuMF): K14c, never a [users x items x width] tensor
+            return fused_pair_full_sort_eval(self.model, eval_data, topk)
         if eval_data.dl_type == DataLoaderType.FULL:
             if self.item_tensor is None:
                 self.item_tensor = eval_data.get_item_feature().to(self.device).repeat(eval_data.step)

@@ -20,6 +20,10 @@ C2 headline (bench.py): one JSON line per configuration, 1 GPU.
   C5  LightGCN, 10M users x 5M items, 100M edges (Zipf items, Zipf-like user
       degrees), d = 256, 2 layers: propagation (K7) once, then full-sort top-10
       (K6) of a bounded sample of users against all 5M items. Unit: users/s.
+  N2  NeuMF at C2's table shape (138,494 x 26,745 rows, widths 64 / 64 / [128, 64, 32]):
+      the pointwise train step (samples/s), the fused full-sort evaluation (K14c, users/s,
+      share of the fp32 MFMA peak) and the generic fallback on a user subset. Not in the
+      default --configs list: --configs N2.
 
 Synthetic data (seeded numpy PCG64 / torch generators), random init. Each step is
 the Trainer's generic step: zero_grad -> calculate_loss -> backward -> FusedAdam.
@@ -563,6 +567,127 @@ def bench_c3_gru4rec(dev, steps, warmup, scale=1.0, B=2048, L=50, E=64, H=128, n
     }
 
 
+def bench_neumf(dev, steps, warmup, scale=1.0, B=2048, K=10, generic_users=256):
+    """NeuMF at C2's table shape (138,494 users x 26,745 items incl. the pad rows, default
+    widths 64 / 64 / [128, 64, 32]): the pointwise train step (B positives + B walk-free
+    uniform negatives with labels, samples/s), the fused full-sort evaluation of every user
+    (K14c, users/s, with the kernel's share of the fp32 MFMA peak at
+    2 * sum H_l H_{l+1} + 2 * dmf flops per pair for layers 2..L) and the generic fallback
+    (fused_eval: False — one user per batch repeated over the catalogue, predict in
+    eval_batch_size pieces, mask, topk) on `generic_users` users."""
+    from recbole_amd import ops
+    from recbole_amd.config import Config
+    from recbole_amd.data.interaction import Interaction
+    from recbole_amd.model.general_recommender import NeuMF
+    from recbole_amd.trainer.optim import FusedAdam
+    from recbole_amd.utils import FeatureType
+    nU, nI = max(2000, int(138_493 * scale)) + 1, max(1000, int(26_744 * scale)) + 1
+    config = Config(model='NeuMF', dataset='ml20m-synth', config_dict={
+        'state': 'ERROR', 'data_path': ROOT, 'load_col': None})
+    config['device'] = dev
+    torch.manual_seed(2020)
+    model = NeuMF(config, StubDataset({'user_id': FeatureType.TOKEN, 'item_id': FeatureType.TOKEN},
+                                      {'user_id': nU, 'item_id': nI})).to(dev)
+    rng = np.random.default_rng(2020)
+    batches = []
+    for _ in range(8):
+        batches.append(Interaction({
+            'user_id': torch.as_tensor(np.tile(rng.integers(1, nU, B), 2)),
+            'item_id': torch.as_tensor(np.r_[_zipf_ids(rng, 1.1, B, nI - 1), rng.integers(1, nI, B)]),
+            'label': torch.as_tensor(np.r_[np.ones(B), np.zeros(B)].astype(np.float32))}).to(dev))
+    opt = FusedAdam(model.parameters(), lr=1e-3, weight_decay=config['weight_decay'])
+    if ADAM_MODE == 'deferred':
+        opt.enable_deferred(model.deferred_tables())
+    it = [0]
+
+    def step():
+        b = batches[it[0] % len(batches)]
+        it[0] += 1
+        opt.zero_grad()
+        model.calculate_loss(b).backward()
+        opt.step()
+
+    t_train = _timed(step, steps, warmup, opt)
+    opt.flush()
+    model.eval()
+    # evaluation inputs: ~20 history items and 1..3 positives per user, sorted CSRs
+    def sorted_rows(width, counts):
+        """Per row up to counts[r] distinct sorted ids of 1..nI-1 as a CSR."""
+        a = np.sort(rng.integers(1, nI, (nU - 1, width)), axis=1)
+        keep = np.ones(a.shape, dtype=bool)
+        keep[:, 1:] = a[:, 1:] != a[:, :-1]
+        keep &= np.cumsum(keep, axis=1) <= counts[:, None]
+        return np.r_[0, np.cumsum(keep.sum(1))].astype(np.int64), a[keep].astype(np.int32)
+
+    hist_ptr, hist_cols = sorted_rows(30, rng.integers(10, 31, nU - 1))
+    pos_ptr, pos_cols = sorted_rows(3, rng.integers(1, 4, nU - 1))
+    D = lambda a: torch.as_tensor(a, device=dev)
+    uids = torch.arange(1, nU, device=dev)
+    hp, hc, pp, pc = D(hist_ptr), D(hist_cols), D(pos_ptr), D(pos_cols)
+    n = uids.numel()
+
+    def fused():
+        scorer = model.fused_pair_scorer()
+        return scorer.topk(uids, K, hist_ptr=hp, hist_cols=hc, pos_ptr=pp, pos_cols=pc)
+
+    with torch.no_grad():
+        fused()
+        torch.cuda.synchronize()
+        t_fused = _event_time(fused, reps=3)
+        ops.KERNEL_EVENTS = {'pair_mlp': []}
+        try:
+            flags = fused()['pos_flags']
+            torch.cuda.synchronize()
+            t_kernel = float(np.mean([a.elapsed_time(b) * 1e-3 for a, b in ops.KERNEL_EVENTS['pair_mlp']]))
+        finally:
+            ops.KERNEL_EVENTS = None
+        test_bs = config['eval_batch_size']
+        items = torch.arange(nI, device=dev)
+        g_n = min(generic_users, n)
+
+        def generic():
+            out = []
+            for q in range(g_n):                     # FULL loader: eval_batch_size // n_items users
+                users = uids[q:q + 1].repeat_interleave(nI)
+                scores = torch.cat([model.predict({'user_id': users[i:i + test_bs],
+                                                   'item_id': items[i:i + test_bs]})
+                                    for i in range(0, nI, test_bs)])
+                scores[0] = -np.inf
+                scores[hc[hist_ptr[q]:hist_ptr[q + 1]].long()] = -np.inf
+                out.append(torch.topk(scores, K).indices)
+            return torch.stack(out)
+
+        generic()
+        torch.cuda.synchronize()
+        t_generic = _event_time(generic, reps=2)
+        g_ids = generic().cpu().numpy()
+        f_ids = fused()['ids'][:g_n].cpu().numpy()
+    hs = list(model.mlp_hidden_size)
+    flops_pair = 2 * sum(a * b for a, b in zip(hs[:-1], hs[1:])) + 2 * model.mf_embedding_size
+    tf = flops_pair * n * nI / t_kernel / 1e12
+    return {
+        'config': 'N2', 'model': 'NeuMF', 'metric': 'train samples/s',
+        'value': round(2 * B / t_train, 1), 'unit': 'samples/s',
+        'ms_per_step': round(t_train * 1e3, 3), 'batch': 2 * B, 'steps': steps,
+        'adam_mode': ADAM_MODE, 'graph_step': False,
+        'eval_fused': {'metric': 'full-sort eval users/s', 'value': round(n / t_fused, 1),
+                       'users': n, 'items': nI, 'seconds': round(t_fused, 4),
+                       'k14c_seconds': round(t_kernel, 4), 'flops_per_pair': flops_pair,
+                       'k14c_tflops': round(tf, 2),
+                       'k14c_frac_of_fp32_mfma_peak': round(tf / MFMA_F32_PEAK_TFLOPS, 3),
+                       'hit_rows': int(flags.any(dim=1).sum().item())},
+        'eval_generic': {'metric': 'full-sort eval users/s (fused_eval: False sequence)',
+                         'value': round(g_n / t_generic, 1), 'users': g_n,
+                         'seconds': round(t_generic, 4),
+                         'ids_equal_to_fused': float((g_ids == f_ids).mean())},
+        'eval_speedup': round((n / t_fused) / (g_n / t_generic), 1),
+        'workload': f'NeuMF ML-20M-shape: {nU:,} users x {nI:,} items (incl. pad rows), '
+                    f'mf 64, mlp 64, hidden {hs}, BCE, weight_decay 1e-8, top-{K}',
+        'dtype': 'fp32', 'data': 'synthetic (uniform users, Zipf(1.1) positives, seeded)',
+        'peak_allocated_MB': round(torch.cuda.max_memory_allocated(dev) / 1e6, 1),
+    }
+
+
 def _c3_ce_record(dev, step, opt, model, batches, loss, steps, warmup, n_items, B, L, d):
     """The C3 step with the full-catalogue cross entropy: sequences/s, the peak allocated
     memory of the run (measured before the loss-only timings below), and the loss's own forward / backward call times (HIP
@@ -770,6 +895,8 @@ def main():
             r = bench_c4(dev, args.steps, args.warmup, args.scale)
         elif c == 'C5':
             r = bench_c5(dev, args.scale)
+        elif c == 'N2':
+            r = bench_neumf(dev, args.steps, args.warmup, args.scale)
         else:
             raise SystemExit(f'unknown config {c}')
         print(json.dumps(r), flush=True)
