@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define MIREC_ABI_VERSION 21
+#define MIREC_ABI_VERSION 22
 
 int mirec_abi_version(void);
 const char* mirec_last_error(void);
@@ -1308,6 +1308,90 @@ int mirec_pair_mlp_f32(const mirec_pair_mlp* mlp, const float* A, const float* P
                        const int32_t* hist_cols, const int64_t* pos_ptr, const int32_t* pos_cols,
                        int32_t K, float* top_scores, int32_t* top_ids, uint8_t* pos_flags,
                        float* scores, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * K15  The autoencoder family's sparse user rows (MultiDAE / MultiVAE,
+ * recbole/model/general_recommender/multidae.py, multivae.py). A batch row b is the SET
+ * S_b of user users[b]'s history items: the slice hist_cols[hist_ptr[u], hist_ptr[u+1]) of
+ * a CSR with distinct, ascending int32 items per user (n_b = its length; a user id outside
+ * [0, n_users) is an empty row, an item outside [0, n_items) is skipped). All fp32, no
+ * atomics: every sum has one owner and a fixed order, so two launches on the same inputs
+ * give the same bits.
+ *
+ * Dropout draws (the project's rule, tests/drop_spec.py): key = splitmix64(splitmix64(seed)
+ * ^ c), c the device counter's value at the forward (kept in drawn[0]); the nonzero (b, item)
+ * is element e = b * n_items + item of the reference's [B, n_items] matrix and is kept iff
+ * the 32-bit half e & 1 of splitmix64(key ^ (e >> 1)) is below min(2^32 - 1, (1 - p) 2^32).
+ *
+ * K15a mirec_bag_linear_fwd_f32 replaces get_rating_matrix + F.normalize + F.dropout + the
+ *   first nn.Linear and its Tanh (multivae.py:54-69, 89-93; multidae.py:51-66, 78-82):
+ *     y[b, :] = act(bias + c_b * sum_{i in S_b, kept} Wt[i, :]),  c_b = 1 / (sqrt(n_b) (1 - p))
+ *   Wt [n_items, N]: the layer's weight stored item-major; N a multiple of 4 in 4..1024; act 0
+ *   none, 1 tanh; an empty row gives act(bias). train != 0 with 0 < p < 1 draws the mask
+ *   (counter, drawn required); otherwise every nonzero is kept and c_b = 1 / sqrt(n_b). The
+ *   backward needs only y (tanh' = 1 - y^2). One workgroup per row; the row is cut into units
+ *   of MIREC_BAG_ROW_SPLIT items, a unit is summed item after item by one wave, and the
+ *   units' partial sums are added in unit order.
+ * K15b, the weight gradient of K15a from G [B, N] (the gradient at the pre-activation):
+ *   mirec_bag_expand_f32 lists the batch's nonzeros, row after row: position q = off[b] + j
+ *   (off [B + 1], the exclusive prefix sums of n_b; nnz = off[B]) gets keys[q] = item (int64,
+ *   the K2 sort's input), row_of[q] = b, wgt[q] = c_b * keep(b, item) with the forward's draw
+ *   recomputed from drawn[0]; with train and p as above it then sets counter[0] = drawn[0] + 1.
+ *   After mirec_segment_sort of keys (stable: equal items keep ascending b),
+ *   mirec_bag_linear_bwd_f32 writes the dense dWt [n_items, N]:
+ *     dWt[i, :] = sum over the batch rows b that contain i, ascending b, of wgt * G[b, :]
+ *   and zeros in every other row: each row is written exactly once (allocate with empty).
+ *   The sorted positions are cut into chunks of MIREC_BAG_SEG_CHUNK, one wave each; an item
+ *   whose positions lie in one chunk is written by that wave, one that crosses a chunk
+ *   boundary is summed from the chunks' partial sums in chunk order. ws: at least
+ *   mirec_bag_linear_bwd_workspace_size(nnz, N) bytes. db is mirec_colsum_f32 of G.
+ * K15c, the multinomial log-likelihood over a stored logits matrix z [B, I], row stride ld
+ *   floats (multivae.py:119, multidae.py:94: -(log_softmax(z) * rating_matrix).sum(1)):
+ *   mirec_multinomial_nll_fwd_f32: lse[b] = logsumexp(z[b, :]) by an online max / sum in one
+ *   read of z, stat[2 b], stat[2 b + 1] = that row's max and sum of exp(z - max), and
+ *   loss_rows[b] = n_b lse[b] - sum_{i in S_b} z[b, i] (formed as the sum of
+ *   lse[b] - z[b, i], which has no cancellation). mirec_multinomial_nll_bwd_f32 overwrites z
+ *   in one read and one write: z[b, i] <- (n_b softmax(z[b])[i] - [i in S_b]) g[0] / B with
+ *   softmax = exp(z - max) / sum from stat (lse rounded to fp32 would cost every term 4e-6
+ *   at |lse| ~ 80), g a device scalar. Any I, any ld >= I: the 16-B aligned body of a row
+ *   moves as float4.
+ * K15d mirec_matrix_topk_f32 ranks a given score matrix [nq, I] (row stride ld) under
+ *   mirec_fullsort_topk_f32's contract: item 0 and the history items of query q (hist CSR
+ *   row q, sorted; NULL = none) are masked, order is (score desc, item id asc), slots past
+ *   the unmasked items get id -1 / score -inf / flag 0, pos_flags[q, r] = the r-th id is in
+ *   pos CSR row q; 1 <= K <= 50. One workgroup per query. Replaces the mask, the topk and
+ *   the pos_idx test of trainer.py:328-353 + evaluators.py:65-75 for models whose scores are
+ *   a matrix and not a dot product of two tables.
+ */
+#define MIREC_BAG_ROW_SPLIT 64
+#define MIREC_BAG_SEG_CHUNK 32
+int mirec_bag_linear_fwd_f32(const int64_t* users, int64_t B, const int64_t* hist_ptr,
+                             const int32_t* hist_cols, int64_t n_users, int64_t n_items,
+                             const float* Wt, const float* bias, int32_t N, float p,
+                             uint64_t seed, const int64_t* counter, int64_t* drawn,
+                             int32_t train, int32_t act, float* y, void* stream);
+int mirec_bag_expand_f32(const int64_t* users, int64_t B, const int64_t* hist_ptr,
+                         const int32_t* hist_cols, int64_t n_users, int64_t n_items,
+                         const int64_t* off, int64_t nnz, float p, uint64_t seed,
+                         const int64_t* drawn, int64_t* counter, int32_t train, int64_t* keys,
+                         int32_t* row_of, float* wgt, void* stream);
+size_t mirec_bag_linear_bwd_workspace_size(int64_t nnz, int32_t N);
+int mirec_bag_linear_bwd_f32(const float* G, int64_t B, int32_t N, int64_t nnz,
+                             const int64_t* keys, const int32_t* row_of, const float* wgt,
+                             const int32_t* perm, int64_t n_items, float* dWt, void* ws,
+                             size_t ws_bytes, void* stream);
+int mirec_multinomial_nll_fwd_f32(const float* z, int64_t ld, int64_t B, int64_t I,
+                                  const int64_t* users, const int64_t* hist_ptr,
+                                  const int32_t* hist_cols, int64_t n_users, float* lse,
+                                  float* stat, float* loss_rows, void* stream);
+int mirec_multinomial_nll_bwd_f32(float* z, int64_t ld, int64_t B, int64_t I,
+                                  const int64_t* users, const int64_t* hist_ptr,
+                                  const int32_t* hist_cols, int64_t n_users, const float* stat,
+                                  const float* g, void* stream);
+int mirec_matrix_topk_f32(const float* scores, int64_t nq, int64_t I, int64_t ld,
+                          const int64_t* hist_ptr, const int32_t* hist_cols,
+                          const int64_t* pos_ptr, const int32_t* pos_cols, int32_t K,
+                          float* top_scores, int32_t* top_ids, uint8_t* pos_flags, void* stream);
 
 #ifdef __cplusplus
 }

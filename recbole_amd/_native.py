@@ -311,9 +311,23 @@ SIGNATURES = {
     "mirec_pair_mlp_supported": (c_int, [_P]),
     "mirec_pair_mlp_f32": (c_int, [_P, _P, _P, c_int64, _P, _P, c_int64, _P, _P, _P, _P, c_int32,
                                    _P, _P, _P, _P, _P]),
+    "mirec_bag_linear_fwd_f32": (c_int, [_P, c_int64, _P, _P, c_int64, c_int64, _P, _P, c_int32,
+                                         c_float, ctypes.c_uint64, _P, _P, c_int32, c_int32, _P,
+                                         _P]),
+    "mirec_bag_expand_f32": (c_int, [_P, c_int64, _P, _P, c_int64, c_int64, _P, c_int64, c_float,
+                                     ctypes.c_uint64, _P, _P, c_int32, _P, _P, _P, _P]),
+    "mirec_bag_linear_bwd_workspace_size": (c_size_t, [c_int64, c_int32]),
+    "mirec_bag_linear_bwd_f32": (c_int, [_P, c_int64, c_int32, c_int64, _P, _P, _P, _P, c_int64,
+                                         _P, _P, c_size_t, _P]),
+    "mirec_multinomial_nll_fwd_f32": (c_int, [_P, c_int64, c_int64, c_int64, _P, _P, _P, c_int64,
+                                              _P, _P, _P, _P]),
+    "mirec_multinomial_nll_bwd_f32": (c_int, [_P, c_int64, c_int64, c_int64, _P, _P, _P, c_int64,
+                                              _P, _P, _P]),
+    "mirec_matrix_topk_f32": (c_int, [_P, c_int64, c_int64, c_int64, _P, _P, _P, _P, c_int32, _P,
+                                      _P, _P, _P]),
 }
 
-ABI_VERSION = 21
+ABI_VERSION = 22
 
 
 class NativeError(RuntimeError):

@@ -189,6 +189,9 @@ class Config(object):
 
     def _set_train_neg_sample_args(self):
         c = self.final_config_dict
+        if c['training_neg_sample_num'] and self.model in ('MultiDAE', 'MultiVAE'):
+            raise ValueError(f'`training_neg_sample_num` should be 0 for {self.model}: its train '
+                             'loader (UserDataLoader) yields users and takes no sampler')
         if c['training_neg_sample_num']:
             c['train_neg_sample_args'] = {
                 'strategy': 'by', 'by': c['training_neg_sample_num'],

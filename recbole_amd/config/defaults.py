@@ -1,6 +1,6 @@
 """Default configuration values, restated as Python data from the reference's
 property files (recbole/properties/overall.yaml, dataset/sample.yaml,
-dataset/ml-100k.yaml, model/{BPR,LightGCN,SASRec,GRU4Rec,DeepFM,NeuMF}.yaml,
+dataset/ml-100k.yaml, model/{BPR,LightGCN,SASRec,GRU4Rec,DeepFM,NeuMF,MultiDAE,MultiVAE}.yaml,
 quick_start_config/{sequential,context-aware}.yaml)."""
 from recbole_amd.utils.enum_type import ModelType
 
@@ -66,6 +66,12 @@ MODEL_DEFAULTS = {
                   dropout_prob=0.0, weight_decay=1e-08, mf_train=True, mlp_train=True,
                   valid_metric='HIT@10', use_pretrain=False, mf_pretrain_path=None,
                   mlp_pretrain_path=None),
+    # training_neg_sample_num=0 is a departure: the reference's MultiDAE / MultiVAE yaml leave
+    # it at the overall 1 and the run dies (UserDataLoader takes no sampler)
+    'MultiDAE': dict(mlp_hidden_size=[600], latent_dimension=64, dropout_prob=0.5,
+                     training_neg_sample_num=0),
+    'MultiVAE': dict(mlp_hidden_size=[600], latent_dimension=128, dropout_prob=0.5,
+                     anneal_cap=0.2, total_anneal_steps=200000, training_neg_sample_num=0),
 }
 
 # quick_start_config/context-aware_ml-100k.yaml, applied after the type preset

@@ -26,6 +26,7 @@ import numpy as np
 import pandas as pd
 import torch
 
+from recbole_amd.data.dlapi import dlapi
 from recbole_amd.data.interaction import Interaction
 from recbole_amd.utils import FeatureSource, FeatureType
 
@@ -842,3 +843,62 @@ class Dataset(object):
         if form == 'csr':
             return mat.tocsr()
         raise NotImplementedError(f'sparse matrix format [{form}] has not been implemented.')
+
+    def _inter_column(self, field):
+        """An interaction column as a numpy array, before build() (a DataFrame) or after."""
+        col = self.inter_feat[field]
+        return col.cpu().numpy() if isinstance(col, torch.Tensor) else np.asarray(col)
+
+    def _history_matrix(self, row, value_field=None):
+        """Padded history of every user (row 'user') or item: ids int64 [n, max_len], values
+        float32 [n, max_len], lengths int64 [n]; a row keeps interaction order, 0 pads
+        (dataset.py:1559-1618, whose per-interaction loop is one stable sort here)."""
+        uids, iids = self._inter_column(self.uid_field), self._inter_column(self.iid_field)
+        if value_field is None:
+            values = np.ones(len(uids))
+        else:
+            if value_field not in self.inter_feat:
+                raise ValueError(f'Value_field [{value_field}] should be one of `inter_feat`\'s '
+                                 'features.')
+            values = self._inter_column(value_field)
+        if row == 'user':
+            row_num, max_col_num, rows, cols = self.user_num, self.item_num, uids, iids
+        else:
+            row_num, max_col_num, rows, cols = self.item_num, self.user_num, iids, uids
+        lens = np.bincount(rows, minlength=row_num).astype(np.int64)
+        col_num = int(lens.max()) if len(rows) else 0
+        if col_num > max_col_num * 0.2:
+            self.logger.warning(f'Max value of {row}\'s history interaction records has reached '
+                                f'{col_num / max_col_num * 100}% of the total.')
+        order = np.argsort(rows, kind='stable')
+        starts = np.cumsum(lens) - lens
+        slot = np.arange(len(rows)) - np.repeat(starts, lens)
+        ids = np.zeros((row_num, col_num), dtype=np.int64)
+        vals = np.zeros((row_num, col_num))
+        ids[rows[order], slot] = cols[order]
+        vals[rows[order], slot] = values[order]
+        return torch.LongTensor(ids), torch.FloatTensor(vals), torch.LongTensor(lens)
+
+    @dlapi.set()
+    def history_item_matrix(self, value_field=None):
+        """(ids, values, lengths) of every user's interacted items (dataset.py:1620-1643)."""
+        return self._history_matrix('user', value_field)
+
+    @dlapi.set()
+    def history_user_matrix(self, value_field=None):
+        """(ids, values, lengths) of every item's interacting users (dataset.py:1645-1668)."""
+        return self._history_matrix('item', value_field)
+
+    @dlapi.set()
+    def history_item_csr(self):
+        """(ptr int64 [n_users + 1], cols int32 [nnz]): every user's DISTINCT items, ascending
+        — the set the autoencoder models read (a repeated interaction counts once, as the
+        reference's non-accumulating index_put_ makes it). nnz-sized, where the padded
+        history_item_matrix is n_users x the longest history."""
+        uids = self._inter_column(self.uid_field).astype(np.int64)
+        iids = self._inter_column(self.iid_field).astype(np.int64)
+        pairs = np.unique(uids * self.item_num + iids)
+        ptr = np.zeros(self.user_num + 1, dtype=np.int64)
+        np.cumsum(np.bincount(pairs // self.item_num, minlength=self.user_num), out=ptr[1:])
+        return torch.from_numpy(ptr), torch.from_numpy((pairs % self.item_num).astype(np.int32))
+

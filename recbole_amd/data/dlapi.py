@@ -25,5 +25,6 @@ class DLFriendlyAPI(object):
 dlapi = DLFriendlyAPI(('num', 'fields', 'token2id', 'token2id_exists', 'id2token', 'user_num',
                        'item_num', 'join', 'get_user_feature', 'get_item_feature',
                        'inter_matrix', 'history_item_matrix', 'history_user_matrix',
+                       'history_item_csr',
                        'get_preload_weight', 'field2type', 'field2source', 'field2id_token',
                        'field2token_id', 'field2seqlen', 'uid_field', 'iid_field'))

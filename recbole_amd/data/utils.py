@@ -29,18 +29,35 @@ _LOADER_FAMILY = {ModelType.GENERAL: 'General', ModelType.TRADITIONAL: 'General'
 _LOADER_KIND = {'none': 'DataLoader', 'by': 'NegSampleDataLoader', 'full': 'FullDataLoader'}
 
 
+# models whose train loader iterates users, not interactions (reference data/utils.py:229-239,
+# _get_AE_data_loader :329-349); their evaluation loaders are the General ones
+_USER_LOADER_MODELS = ('MultiDAE', 'MultiVAE')
+
+
 def get_data_loader(name, config, neg_sample_args):
-    """Loader class for phase `name` ('train' / 'evaluation'): the class named
-    `<family><kind>` in the dataloader package, as the reference looks it up. The
-    reference's per-model table (DIN, DIEN, the autoencoders) and the fork's
-    dataset-negative / both-way loaders belong to model families outside this build."""
-    model_type = config['MODEL_TYPE']
+    """Loader class for phase `name` ('train' / 'evaluation'): the per-model table first
+    (MultiDAE / MultiVAE: UserDataLoader for training, the General loader of the strategy
+    for evaluation), otherwise the class named `<family><kind>` in the dataloader package,
+    as the reference looks it up. The rest of the reference's per-model table (DIN, DIEN,
+    the other autoencoders) and the fork's dataset-negative / both-way loaders belong to
+    model families outside this build."""
     strategy = neg_sample_args['strategy']
+    loaders = importlib.import_module('recbole_amd.data.dataloader')
+    try:
+        model = config['model']
+    except KeyError:                          # a bare mapping without the key
+        model = None
+    if model in _USER_LOADER_MODELS:
+        if name == 'train':
+            return loaders.UserDataLoader
+        if strategy not in _LOADER_KIND:
+            raise NotImplementedError(f'neg_sample strategy [{strategy}] is not implemented')
+        return getattr(loaders, 'General' + _LOADER_KIND[strategy])
+    model_type = config['MODEL_TYPE']
     if model_type not in _LOADER_FAMILY:
         raise NotImplementedError(f'Model_type [{model_type}] has not been implemented.')
     if strategy not in _LOADER_KIND:
         raise NotImplementedError(f'neg_sample strategy [{strategy}] is not implemented')
-    loaders = importlib.import_module('recbole_amd.data.dataloader')
     return getattr(loaders, _LOADER_FAMILY[model_type] + _LOADER_KIND[strategy])
 
 

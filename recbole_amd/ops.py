@@ -1145,6 +1145,167 @@ def pair_mlp_scores(desc, A, Pq, Bm, I_mf, out=None):
     return out
 
 
+# ---------------------------------------------------------------- K15 sparse user rows
+BAG_ROW_SPLIT = 64       # MIREC_BAG_ROW_SPLIT (include/mirec.h): items per K15a unit
+BAG_SEG_CHUNK = 32       # MIREC_BAG_SEG_CHUNK: sorted positions per K15b wave
+
+
+def _hist(users, hist_ptr, hist_cols):
+    _dev(users, torch.int64, "users")
+    _dev(hist_ptr, torch.int64, "hist_ptr")
+    _dev(hist_cols, torch.int32, "hist_cols")
+    return hist_ptr.numel() - 1
+
+
+def colsum(x, out=None):
+    """out[j] = sum_i x[i, j] in row order (mirec_colsum_f32: fixed order, bias gradients)."""
+    _dev(x, torch.float32, "x")
+    n, m = x.shape
+    if out is None:
+        out = torch.empty(m, dtype=torch.float32, device=x.device)
+    check(lib().mirec_colsum_f32(ptr(x), n, m, ptr(out), stream_handle()), "mirec_colsum_f32")
+    return out
+
+
+def bag_linear_fwd(users, hist_ptr, hist_cols, Wt, bias, p: float = 0.0, rng=None,
+                   train: bool = False, tanh: bool = False, drawn=None):
+    """K15a: y [B, N] = act(bias + c_b * sum of the kept rows Wt[i], i in the history set of
+    users[b]); Wt [n_items, N] item-major, N a multiple of 4 in 4..1024. With train and
+    0 < p < 1, rng = (seed, device int64 counter) keys the draw and `drawn` (device int64
+    [1]) receives the counter value used."""
+    n_users = _hist(users, hist_ptr, hist_cols)
+    _dev(Wt, torch.float32, "Wt")
+    _dev(bias, torch.float32, "bias")
+    n_items, N = Wt.shape
+    B = users.numel()
+    drop = bool(train) and p > 0
+    seed, counter = rng if drop else (0, None)
+    y = torch.empty(B, N, dtype=torch.float32, device=Wt.device)
+    with timed_launch('bag_fwd'):
+        rc = lib().mirec_bag_linear_fwd_f32(ptr(users), B, ptr(hist_ptr), ptr(hist_cols), n_users,
+                                            n_items, ptr(Wt), ptr(bias), N, float(p), seed,
+                                            ptr(counter), ptr(drawn), int(drop), int(bool(tanh)),
+                                            ptr(y), stream_handle())
+    check(rc, "mirec_bag_linear_fwd_f32")
+    return y
+
+
+def bag_row_offsets(users, hist_ptr):
+    """(off int64 [B + 1], nnz): the exclusive prefix sums of the batch rows' lengths and
+    their total — the ONE host read of a K15 step (it sizes the K15b launches)."""
+    lens = hist_ptr[users + 1] - hist_ptr[users]
+    off = torch.zeros(users.numel() + 1, dtype=torch.int64, device=users.device)
+    torch.cumsum(lens, 0, out=off[1:])
+    return off, int(off[-1].item())
+
+
+def bag_linear_bwd(G, users, hist_ptr, hist_cols, n_items: int, p: float = 0.0, rng=None,
+                   train: bool = False, drawn=None, offsets=None):
+    """K15b: the dense dWt [n_items, N] of K15a for G [B, N], the gradient at the
+    pre-activation: expand the batch's nonzeros (the forward's draw recomputed from
+    `drawn`, the counter advanced), group them by item (K2, stable) and sum
+    weight * G[row] through the permutation, ascending batch row. Every row is written."""
+    n_users = _hist(users, hist_ptr, hist_cols)
+    _dev(G, torch.float32, "G")
+    B, N = G.shape
+    dev = G.device
+    off, nnz = offsets if offsets is not None else bag_row_offsets(users, hist_ptr)
+    drop = bool(train) and p > 0
+    seed, counter = rng if drop else (0, None)
+    keys = torch.empty(max(nnz, 1), dtype=torch.int64, device=dev)
+    row_of = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)
+    wgt = torch.empty(max(nnz, 1), dtype=torch.float32, device=dev)
+    rc = lib().mirec_bag_expand_f32(ptr(users), B, ptr(hist_ptr), ptr(hist_cols), n_users,
+                                    n_items, ptr(off), nnz, float(p), seed, ptr(drawn),
+                                    ptr(counter), int(drop), ptr(keys), ptr(row_of), ptr(wgt),
+                                    stream_handle())
+    check(rc, "mirec_bag_expand_f32")
+    dWt = torch.empty(n_items, N, dtype=torch.float32, device=dev)       # every row written
+    perm, ws, wsz = None, None, 0
+    if nnz > 0:
+        segs = segment_sort(keys[:nnz], n_items)
+        perm = segs.perm
+        wsz = lib().mirec_bag_linear_bwd_workspace_size(nnz, N)
+        ws = torch.empty(wsz, dtype=torch.uint8, device=dev)
+    with timed_launch('bag_bwd'):
+        rc = lib().mirec_bag_linear_bwd_f32(ptr(G), B, N, nnz, ptr(keys), ptr(row_of), ptr(wgt),
+                                            ptr(perm), n_items, ptr(dWt), ptr(ws), wsz,
+                                            stream_handle())
+    check(rc, "mirec_bag_linear_bwd_f32")
+    return dWt
+
+
+def _logits_ld(z):
+    """Row stride of a float32 [B, I] device matrix whose rows are contiguous."""
+    if not isinstance(z, torch.Tensor):
+        raise TypeError("the matrix must be a torch.Tensor")
+    if not z.is_cuda:
+        raise NativeError(f"the matrix must live on the GPU (got {z.device}); no CPU fallback "
+                          "exists")
+    if z.dtype != torch.float32 or z.dim() != 2 or z.stride(1) != 1 or z.stride(0) < z.shape[1]:
+        raise ValueError("the matrix must be float32 [B, I] with unit column stride and row "
+                         "stride >= I")
+    return z.stride(0)
+
+
+def multinomial_nll_fwd(z, users, hist_ptr, hist_cols):
+    """K15c forward: (lse [B], loss_rows [B], stat [B, 2]) of the stored logits z [B, I] (a
+    row-strided view is taken as it is); loss_rows[b] = n_b lse[b] - sum of z[b, i] over the
+    history set, stat[b] = the row's (max, sum of exp(z - max)), which the backward reads."""
+    n_users = _hist(users, hist_ptr, hist_cols)
+    ld = _logits_ld(z)
+    B, I = z.shape
+    lse = torch.empty(B, dtype=torch.float32, device=z.device)
+    stat = torch.empty(B, 2, dtype=torch.float32, device=z.device)
+    loss_rows = torch.empty(B, dtype=torch.float32, device=z.device)
+    rc = lib().mirec_multinomial_nll_fwd_f32(ptr(z), ld, B, I, ptr(users), ptr(hist_ptr),
+                                             ptr(hist_cols), n_users, ptr(lse), ptr(stat),
+                                             ptr(loss_rows), stream_handle())
+    check(rc, "mirec_multinomial_nll_fwd_f32")
+    return lse, loss_rows, stat
+
+
+def multinomial_nll_bwd_(z, users, hist_ptr, hist_cols, stat, g):
+    """K15c backward, IN PLACE: z[b, i] <- (n_b softmax(z[b])[i] - [i in the set]) g / B, from
+    the forward's stat; g a one-element device tensor (no host sync). Returns z."""
+    n_users = _hist(users, hist_ptr, hist_cols)
+    ld = _logits_ld(z)
+    _dev(stat, torch.float32, "stat")
+    _dev(g, torch.float32, "g")
+    B, I = z.shape
+    if stat.numel() != 2 * B or g.numel() != 1:
+        raise ValueError("multinomial_nll_bwd_: shapes differ")
+    rc = lib().mirec_multinomial_nll_bwd_f32(ptr(z), ld, B, I, ptr(users), ptr(hist_ptr),
+                                             ptr(hist_cols), n_users, ptr(stat), ptr(g),
+                                             stream_handle())
+    check(rc, "mirec_multinomial_nll_bwd_f32")
+    return z
+
+
+def matrix_topk(scores, K: int, hist_ptr=None, hist_cols=None, pos_ptr=None, pos_cols=None,
+                out: dict | None = None) -> dict:
+    """K15d: fullsort_topk's outputs for a GIVEN score matrix [nq, I] (a row-strided view is
+    taken as it is): item 0 and the history masked, (score desc, id asc), 1 <= K <= 50."""
+    ld = _logits_ld(scores)
+    for n_, t_, dt in (("hist_ptr", hist_ptr, torch.int64), ("hist_cols", hist_cols, torch.int32),
+                       ("pos_ptr", pos_ptr, torch.int64), ("pos_cols", pos_cols, torch.int32)):
+        if t_ is not None:
+            _dev(t_, dt, n_)
+    nq, I = scores.shape
+    o = {} if out is None else out
+    dev = scores.device
+    o.setdefault("scores", torch.empty(nq, K, dtype=torch.float32, device=dev))
+    o.setdefault("ids", torch.empty(nq, K, dtype=torch.int32, device=dev))
+    if pos_ptr is not None:
+        o.setdefault("pos_flags", torch.empty(nq, K, dtype=torch.uint8, device=dev))
+    with timed_launch('matrix_topk'):
+        rc = lib().mirec_matrix_topk_f32(ptr(scores), nq, I, ld, ptr(hist_ptr), ptr(hist_cols),
+                                         ptr(pos_ptr), ptr(pos_cols), K, ptr(o["scores"]),
+                                         ptr(o["ids"]), ptr(o.get("pos_flags")), stream_handle())
+    check(rc, "mirec_matrix_topk_f32")
+    return o
+
+
 # ---------------------------------------------------------------- K12 full-catalogue CE
 def full_ce_splits(B: int, I: int, d: int, splits: int = 0) -> int:
     """The item split K12 uses for `splits` (0 = auto): a host-side pure function."""

@@ -1,5 +1,5 @@
 """Evaluation on the fused kernels: full-sort top-K (K6) for general and sequential
-models, and the sampled (uni-N / pop-N) evaluations, for Trainer.evaluate."""
+models, K14c / K15d for models scored by an MLP or a matrix, and the sampled (uni-N / pop-N) evaluations, for Trainer.evaluate."""
 from __future__ import annotations
 
 import numpy as np
@@ -55,6 +55,33 @@ def fused_pair_full_sort_eval(model, eval_data, topk_evaluator, user_batch=1 << 
         scorer.topk(uids[s:e], K, hist_ptr=hist_ptr[s:e + 1], hist_cols=hist_cols,
                     pos_ptr=pos_ptr[s:e + 1], pos_cols=pos_cols,
                     out={'pos_flags': flags[s:e]})
+    pos_idx = flags.cpu().numpy().astype(bool)
+    return topk_evaluator.evaluate_pos_idx(pos_idx, eval_data.get_pos_len_list())
+
+
+MATRIX_EVAL_BYTES = 256 << 20      # budget of one user block's score matrix
+
+
+def fused_matrix_full_sort_eval(model, eval_data, topk_evaluator, user_batch=None):
+    """Trainer.evaluate for a FULL loader and a model whose scores are a matrix and not a dot
+    product of two tables (MultiDAE, MultiVAE): per user block, model.fused_matrix_scorer()
+    forms the [block, n_items] logits and K15d (ops.matrix_topk) applies the pad / history
+    mask, takes the top-K and tests the positives; only the [n_users, K] flags go to the
+    host. user_batch defaults to the largest block whose score matrix stays within
+    MATRIX_EVAL_BYTES = 256 MiB (2,509 users at 26,745 items). One GPU."""
+    scorer = model.fused_matrix_scorer()
+    dev = scorer.device
+    K = max(topk_evaluator.topk)
+    uids, hist_ptr, hist_cols, pos_ptr, pos_cols = eval_data.device_csr(dev)
+    n = uids.numel()
+    if user_batch is None:
+        user_batch = max(1, MATRIX_EVAL_BYTES // (4 * model.n_items))
+    flags = torch.empty(n, K, dtype=torch.uint8, device=dev)
+    for s in range(0, n, user_batch):
+        e = min(n, s + user_batch)
+        ops.matrix_topk(scorer.scores(uids[s:e]), K, hist_ptr=hist_ptr[s:e + 1],
+                        hist_cols=hist_cols, pos_ptr=pos_ptr[s:e + 1], pos_cols=pos_cols,
+                        out={'pos_flags': flags[s:e]})
     pos_idx = flags.cpu().numpy().astype(bool)
     return topk_evaluator.evaluate_pos_idx(pos_idx, eval_data.get_pos_len_list())
 

@@ -13,7 +13,8 @@ checkpoint dict as the reference. Two execution paths:
 
 Evaluation of a FULL loader uses the fused K6 scorer when the model provides
 fused_user_vectors()/fused_item_table(), the fused pair-MLP scorer (K14c) when it
-provides fused_pair_scorer(); otherwise the reference's full_sort_predict + mask +
+provides fused_pair_scorer(), the matrix ranker (K15d) when it provides
+fused_matrix_scorer(); otherwise the reference's full_sort_predict + mask +
 swap + TopKEvaluator.collect sequence.
 
 Documented difference: the NaN check of the fused path runs once per epoch
@@ -37,6 +38,7 @@ from recbole_amd.data.dataloader.sequential_dataloader import SequentialNegSampl
 from recbole_amd.sampler import RepeatableSampler
 from recbole_amd.trainer.fused import FusedBPRTrainStep
 from recbole_amd.trainer.fused_eval import (fused_full_sort_eval, fused_general_sampled_eval,
+                                            fused_matrix_full_sort_eval,
                                             fused_pair_full_sort_eval, fused_seq_full_sort_eval,
                                             fused_seq_sampled_eval)
 from recbole_amd.trainer.sharded import ShardedBPRTrainStep
@@ -392,6 +394,12 @@ class Trainer(AbstractTrainer):
                 and max(topk.topk) <= 50 and self.model.pair_scorer_applies()):
             # a per-pair MLP score (NeuMF): K14c, never a [users x items x width] tensor
             return fused_pair_full_sort_eval(self.model, eval_data, topk)
+        if (eval_data.dl_type == DataLoaderType.FULL and self.config['fused_eval'] is not False
+                and hasattr(self.model, 'fused_matrix_scorer') and self._dp is None
+                and topk is not None and len(self.evaluator.evaluators) == 1
+                and max(topk.topk) <= 50 and self.model.fused_matrix_scorer() is not None):
+            # scores that are a matrix (MultiDAE, MultiVAE): K15d ranks each user block
+            return fused_matrix_full_sort_eval(self.model, eval_data, topk)
         if eval_data.dl_type == DataLoaderType.FULL:
             if self.item_tensor is None:
                 self.item_tensor = eval_data.get_item_feature().to(self.device).repeat(eval_data.step)

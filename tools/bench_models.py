@@ -24,6 +24,11 @@ C2 headline (bench.py): one JSON line per configuration, 1 GPU.
       the pointwise train step (samples/s), the fused full-sort evaluation (K14c, users/s,
       share of the fp32 MFMA peak) and the generic fallback on a user subset. Not in the
       default --configs list: --configs N2.
+  A2  MultiVAE at C2's table shape and interaction count (synthetic Zipf histories, default
+      widths 600 / 128, B = 2,048 users): the K15 train step against a dense fp32 torch
+      statement of the reference's step on the same device, weights and batches (ms/step,
+      users/s, peak allocated), and the full-sort evaluation, fused (K15d) against the
+      generic sequence on a user subset. Not in the default list: --configs A2.
 
 Synthetic data (seeded numpy PCG64 / torch generators), random init. Each step is
 the Trainer's generic step: zero_grad -> calculate_loss -> backward -> FusedAdam.
@@ -688,6 +693,140 @@ def bench_neumf(dev, steps, warmup, scale=1.0, B=2048, K=10, generic_users=256):
     }
 
 
+def bench_multivae(dev, steps, warmup, scale=1.0, B=2048, K=10, generic_users=256):
+    """MultiVAE at C2's table shape (138,494 users x 26,745 items incl. the pad rows, the
+    synthetic ml-20m-shape interactions of bench.make_c2 as every user's history), default
+    widths (600, latent 128, dropout 0.5), B users per step.
+
+    train: the K15 step (K15a -> layers -> addmm -> K15c, backward K15c in place / K15b)
+      against a DENSE statement of the reference's step written here with torch ops: the
+      [B, n_items] rating matrix by index_put_, F.normalize, F.dropout, the encoder's first
+      layer as a dense GEMM, log_softmax(z) * rating_matrix. Same device, same initial
+      weights, same user batches, FusedAdam for both; peak allocated bytes of each.
+    eval: every user's full-sort top-K, fused (score blocks of MATRIX_EVAL_BYTES + K15d)
+      against the generic sequence (full_sort_predict, the pad / history mask, torch.topk;
+      one user per batch, as eval_batch_size 4,096 gives at this catalogue) on
+      `generic_users` users."""
+    import copy
+
+    import torch.nn.functional as F
+
+    import bench
+    from recbole_amd import ops
+    from recbole_amd.config import Config
+    from recbole_amd.data.dataset import Dataset
+    from recbole_amd.model.general_recommender import MultiVAE
+    from recbole_amd.trainer.fused_eval import MATRIX_EVAL_BYTES
+    from recbole_amd.trainer.optim import FusedAdam
+    n_u, n_i = max(2000, int(138_493 * scale)), max(1000, int(26_744 * scale))
+    u, i, nU, nI = bench.make_c2(2020, n_u, n_i, int(20_000_263 * scale))
+    config = Config(model='MultiVAE', dataset='ml20m-synth', config_dict={
+        'state': 'ERROR', 'data_path': ROOT, 'load_col': None})
+    config['device'] = dev
+    torch.manual_seed(2020)
+    model = MultiVAE(config, Dataset.from_interactions(config, u, i, nU, nI)).to(dev)
+    dense = copy.deepcopy(model)
+    nnz_row = model.hist_cols.numel() / (nU - 1)
+    rng = np.random.default_rng(2020)
+    batches = [torch.as_tensor(rng.integers(0, nU, B)).to(dev) for _ in range(8)]
+
+    def runner(m, loss_fn):
+        opt = FusedAdam(m.parameters(), lr=1e-3, weight_decay=config['weight_decay'])
+        it = [0]
+
+        def step():
+            b = batches[it[0] % len(batches)]
+            it[0] += 1
+            opt.zero_grad()
+            loss_fn(m, b).backward()
+            opt.step()
+        return step, opt
+
+    def dense_loss(m, user):
+        m.update += 1
+        anneal = min(m.anneal_cap, m.update / m.total_anneal_steps)
+        R = m.get_rating_matrix(user)
+        h = m.encoder(F.dropout(F.normalize(R), m.drop_out, training=True))
+        half = m.lat_dim // 2
+        mu, logvar = h[:, :half], h[:, half:]
+        z = m.decoder(mu + torch.zeros_like(logvar).normal_(0, 0.01) * torch.exp(0.5 * logvar))
+        kl = -0.5 * torch.mean(torch.sum(1 + logvar - mu.pow(2) - logvar.exp(), dim=1)) * anneal
+        return -(F.log_softmax(z, 1) * R).sum(1).mean() + kl
+
+    out = {}
+    for name, m, fn in (('k15', model, lambda m, b: m.calculate_loss({'user_id': b})),
+                        ('dense', dense, dense_loss)):
+        m.train()
+        step, opt = runner(m, fn)
+        step()
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats(dev)
+        t = _timed(step, steps, warmup, opt)
+        out[name] = {'ms_per_step': round(t * 1e3, 3), 'users_per_s': round(B / t, 1),
+                     'peak_allocated_MB': round(torch.cuda.max_memory_allocated(dev) / 1e6, 1)}
+        del step, opt
+    del dense
+    torch.cuda.empty_cache()
+
+    model.eval()
+    uids = torch.arange(1, nU, device=dev)
+    n = uids.numel()
+    hp, hc = model.hist_ptr[1:].contiguous(), model.hist_cols      # users 1.. of the CSR
+    pos = np.sort(rng.integers(1, nI, (n, 2)), axis=1)
+    pp = torch.arange(0, 2 * n + 1, 2, device=dev)
+    pc = torch.as_tensor(pos.reshape(-1).astype(np.int32), device=dev)
+    block = max(1, MATRIX_EVAL_BYTES // (4 * nI))
+    g_n = min(generic_users, n)
+
+    def fused(count=n):
+        scorer = model.fused_matrix_scorer()
+        flags = torch.empty(count, K, dtype=torch.uint8, device=dev)
+        ids = torch.empty(count, K, dtype=torch.int32, device=dev)
+        for s0 in range(0, count, block):
+            e0 = min(count, s0 + block)
+            ops.matrix_topk(scorer.scores(uids[s0:e0]), K, hist_ptr=hp[s0:e0 + 1], hist_cols=hc,
+                            pos_ptr=pp[s0:e0 + 1], pos_cols=pc,
+                            out={'pos_flags': flags[s0:e0], 'ids': ids[s0:e0]})
+        return flags, ids
+
+    def generic():
+        res = []
+        for q in range(g_n):
+            scores = model.full_sort_predict({'user_id': uids[q:q + 1]}).view(1, nI)
+            scores[:, 0] = -np.inf
+            scores[0, hc[hp[q]:hp[q + 1]].long()] = -np.inf
+            res.append(torch.topk(scores, K).indices)
+        return torch.cat(res)
+
+    with torch.no_grad():
+        fused()
+        torch.cuda.synchronize()
+        t_fused = _event_time(fused, reps=3)
+        generic()
+        torch.cuda.synchronize()
+        t_generic = _event_time(generic, reps=2)
+        same = float((generic().cpu().numpy() == fused(g_n)[1].cpu().numpy()).mean())
+    return {
+        'config': 'A2', 'model': 'MultiVAE', 'metric': 'train users/s',
+        'value': out['k15']['users_per_s'], 'unit': 'users/s', 'batch': B, 'steps': steps,
+        'train_k15': out['k15'], 'train_dense_torch': out['dense'],
+        'train_speedup': round(out['dense']['ms_per_step'] / out['k15']['ms_per_step'], 2),
+        'eval_fused': {'metric': 'full-sort eval users/s', 'value': round(n / t_fused, 1),
+                       'users': n, 'seconds': round(t_fused, 4), 'users_per_block': block},
+        'eval_generic': {'metric': 'full-sort eval users/s (fused_eval: False sequence)',
+                         'value': round(g_n / t_generic, 1), 'users': g_n,
+                         'seconds': round(t_generic, 4), 'ids_equal_to_fused': same},
+        'eval_speedup': round((n / t_fused) / (g_n / t_generic), 1),
+        'workload': f'MultiVAE ML-20M-shape: {nU:,} users x {nI:,} items (incl. pad rows), '
+                    f'{model.hist_cols.numel():,} interactions ({nnz_row:.1f} per user), hidden '
+                    f'{list(model.layers)}, latent {model.lat_dim}, dropout {model.drop_out}, '
+                    f'top-{K}',
+        'dtype': 'fp32', 'graph_step': False,
+        'data': 'synthetic (bench.make_c2: lognormal user activity, Zipf items, seeded)',
+        'sample': 'one run; spread not measured',
+    }
+
+
 def _c3_ce_record(dev, step, opt, model, batches, loss, steps, warmup, n_items, B, L, d):
     """The C3 step with the full-catalogue cross entropy: sequences/s, the peak allocated
     memory of the run (measured before the loss-only timings below), and the loss's own forward / backward call times (HIP
@@ -897,6 +1036,8 @@ def main():
             r = bench_c5(dev, args.scale)
         elif c == 'N2':
             r = bench_neumf(dev, args.steps, args.warmup, args.scale)
+        elif c == 'A2':
+            r = bench_multivae(dev, args.steps, args.warmup, args.scale)
         else:
             raise SystemExit(f'unknown config {c}')
         print(json.dumps(r), flush=True)
