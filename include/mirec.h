@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define MIREC_ABI_VERSION 22
+#define MIREC_ABI_VERSION 23
 
 int mirec_abi_version(void);
 const char* mirec_last_error(void);
@@ -1392,6 +1392,55 @@ int mirec_matrix_topk_f32(const float* scores, int64_t nq, int64_t I, int64_t ld
                           const int64_t* hist_ptr, const int32_t* hist_cols,
                           const int64_t* pos_ptr, const int32_t* pos_cols, int32_t K,
                           float* top_scores, int32_t* top_ids, uint8_t* pos_flags, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * K16 — NGCF's bi-interaction layer (csrc/ngcf.hip; reference ngcf.py:132-147, BiGNNLayer
+ * layers.py:174-197). x = A_hat' E_l comes from mirec_spmm_csr_f32.
+ * A rows operand is (lo, hi, split, ld): row r at lo + r ld for r < split, else at
+ * hi + (r - split) ld (hi NULL: every row from lo). lo / hi 16-byte aligned, ld % 4 == 0.
+ * Widths (d_in, d_out) in {64, 128}^2 (mirec_ngcf_shape_ok); anything else is an error.
+ * Dropout p in [0, 1): p = 0 draws nothing and ignores seed / counter / drawn; p > 0 uses
+ * K9d's counter-based draws (element e = row d_out + column): the forward reads
+ * counter[0] into drawn[0], the backward redraws from drawn[0] and sets counter[0] to
+ * drawn[0] + 1.
+ *
+ * forward:  z = (E + x) W1^T + b1 + (x * E) W2^T + b2;  m = dropout(leaky_relu_0.2(z));
+ *           out[r] = m / max(||m||, 1e-12);  copy[r] = out[r] (optional, contiguous
+ *           [n, d_out]);  nrm[r] = ||m||.
+ * backward: G the gradient of out, E_next = out;  g_z -> gz [n, d_out];
+ *           dE = g_z W1 + (g_z W2) * x (+ add);  gx = g_z W1 + (g_z W2) * E  (both
+ *           contiguous [n, d_in]; the caller finishes dE_l = A_hat'^T gx + dE with K7).
+ * wgrad:    partials [mirec_ngcf_wgrad_splits(n), d_out, 2 d_in]: block b's rows' sum of
+ *           g_z^T (E + x | x * E), rows in order; mirec_linear_grad_finish_f32 adds them in
+ *           block order (columns [0, d_in) are dW1, the rest dW2) and forms db from gz.
+ * ------------------------------------------------------------------------- */
+typedef struct mirec_rows_ld {
+  float* lo;
+  float* hi;
+  int64_t split;
+  int64_t ld;
+} mirec_rows_ld;
+
+/* mirec_ngcf_grid_cap(w): w > 0 caps the workgroups of the two persistent kernels (forward,
+ * backward) at w, 0 lifts the cap, w < 0 only asks; returns the cap before the call. Outputs do
+ * not depend on it bit for bit (the tests use it to make a wave walk many slabs at a small n).
+ */
+int32_t mirec_ngcf_grid_cap(int32_t workgroups);
+int mirec_ngcf_shape_ok(int32_t d_in, int32_t d_out);
+int mirec_ngcf_layer_fwd_f32(const mirec_rows_ld* E, const float* x, int64_t n, int32_t d_in,
+                             int32_t d_out, const float* W1, const float* b1, const float* W2,
+                             const float* b2, const mirec_rows_ld* out, float* copy, float* nrm,
+                             float p, uint64_t seed, int64_t* counter, int64_t* drawn,
+                             void* stream);
+int mirec_ngcf_layer_bwd_f32(const mirec_rows_ld* G, const mirec_rows_ld* E_next,
+                             const float* nrm, int64_t n, int32_t d_in, int32_t d_out,
+                             const float* W1, const float* W2, const mirec_rows_ld* E,
+                             const float* x, const mirec_rows_ld* add, float* gz, float* dE,
+                             float* gx, float p, uint64_t seed, int64_t* drawn, int64_t* counter,
+                             void* stream);
+int32_t mirec_ngcf_wgrad_splits(int64_t n);
+int mirec_ngcf_wgrad_f32(const float* gz, const mirec_rows_ld* E, const float* x, int64_t n,
+                         int32_t d_in, int32_t d_out, float* partials, void* stream);
 
 #ifdef __cplusplus
 }

@@ -27,6 +27,11 @@ class RowsRef(ctypes.Structure):
     _fields_ = [('lo', _P), ('hi', _P), ('split', c_int64)]
 
 
+class RowsLd(ctypes.Structure):
+    """struct mirec_rows_ld (include/mirec.h, K16)."""
+    _fields_ = [('lo', _P), ('hi', _P), ('split', c_int64), ('ld', c_int64)]
+
+
 class SpmmEpilogue(ctypes.Structure):
     """struct mirec_spmm_epilogue (include/mirec.h)."""
     _fields_ = [('add', RowsRef), ('add_scale', c_float), ('y', RowsRef), ('acc_in', RowsRef),
@@ -325,9 +330,21 @@ SIGNATURES = {
                                               _P, _P, _P]),
     "mirec_matrix_topk_f32": (c_int, [_P, c_int64, c_int64, c_int64, _P, _P, _P, _P, c_int32, _P,
                                       _P, _P, _P]),
+    "mirec_ngcf_grid_cap": (c_int32, [c_int32]),
+    "mirec_ngcf_shape_ok": (c_int, [c_int32, c_int32]),
+    "mirec_ngcf_layer_fwd_f32": (c_int, [ctypes.POINTER(RowsLd), _P, c_int64, c_int32, c_int32,
+                                         _P, _P, _P, _P, ctypes.POINTER(RowsLd), _P, _P, c_float,
+                                         ctypes.c_uint64, _P, _P, _P]),
+    "mirec_ngcf_layer_bwd_f32": (c_int, [ctypes.POINTER(RowsLd), ctypes.POINTER(RowsLd), _P,
+                                         c_int64, c_int32, c_int32, _P, _P,
+                                         ctypes.POINTER(RowsLd), _P, ctypes.POINTER(RowsLd), _P,
+                                         _P, _P, c_float, ctypes.c_uint64, _P, _P, _P]),
+    "mirec_ngcf_wgrad_splits": (c_int32, [c_int64]),
+    "mirec_ngcf_wgrad_f32": (c_int, [_P, ctypes.POINTER(RowsLd), _P, c_int64, c_int32, c_int32,
+                                     _P, _P]),
 }
 
-ABI_VERSION = 22
+ABI_VERSION = 23
 
 
 class NativeError(RuntimeError):

@@ -1,6 +1,6 @@
 """Default configuration values, restated as Python data from the reference's
 property files (recbole/properties/overall.yaml, dataset/sample.yaml,
-dataset/ml-100k.yaml, model/{BPR,LightGCN,SASRec,GRU4Rec,DeepFM,NeuMF,MultiDAE,MultiVAE}.yaml,
+dataset/ml-100k.yaml, model/{BPR,LightGCN,NGCF,SASRec,GRU4Rec,DeepFM,NeuMF,MultiDAE,MultiVAE}.yaml,
 quick_start_config/{sequential,context-aware}.yaml)."""
 from recbole_amd.utils.enum_type import ModelType
 
@@ -56,6 +56,8 @@ DATASET_DEFAULTS = {
 MODEL_DEFAULTS = {
     'BPR': dict(embedding_size=64),
     'LightGCN': dict(embedding_size=64, n_layers=2, reg_weight=1e-05),
+    'NGCF': dict(embedding_size=64, hidden_size_list=[64, 64, 64], node_dropout=0.0,
+                 message_dropout=0.1, reg_weight=1e-05),
     'SASRec': dict(n_layers=2, n_heads=2, hidden_size=64, inner_size=256,
                    hidden_dropout_prob=0.5, attn_dropout_prob=0.5, hidden_act='gelu',
                    layer_norm_eps=1e-12, initializer_range=0.02, loss_type='CE'),

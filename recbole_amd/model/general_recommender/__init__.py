@@ -3,5 +3,6 @@ from recbole_amd.model.general_recommender.lightgcn import LightGCN
 from recbole_amd.model.general_recommender.multidae import MultiDAE
 from recbole_amd.model.general_recommender.multivae import MultiVAE
 from recbole_amd.model.general_recommender.neumf import NeuMF
+from recbole_amd.model.general_recommender.ngcf import NGCF
 
-__all__ = ['BPR', 'LightGCN', 'MultiDAE', 'MultiVAE', 'NeuMF']
+__all__ = ['BPR', 'LightGCN', 'MultiDAE', 'MultiVAE', 'NGCF', 'NeuMF']

@@ -720,3 +720,46 @@ class TransformerEncoder(nn.Module):
         if not output_all_encoded_layers:
             out.append(hidden_states)
         return out
+
+
+class BiGNNLayer(nn.Module):
+    """NGCF's bi-interaction layer (layers.py:174-197): with x = L E,
+    linear(E + x) + interActTransform(x * E). These are the torch ops; on the GPU NGCF
+    runs the layer, its activation, dropout and row normalisation in K16 (csrc/ngcf.hip)
+    over this module's weights."""
+
+    def __init__(self, in_dim, out_dim):
+        super().__init__()
+        self.in_dim = in_dim
+        self.out_dim = out_dim
+        self.linear = nn.Linear(in_features=in_dim, out_features=out_dim)
+        self.interActTransform = nn.Linear(in_features=in_dim, out_features=out_dim)
+
+    def forward(self, lap_matrix, eye_matrix, features):
+        x = torch.sparse.mm(lap_matrix, features)
+        return self.linear(features + x) + self.interActTransform(x * features)
+
+
+class SparseDropout(nn.Module):
+    """Dropout over the stored values of a sparse matrix (layers.py:1064-1082): entry k is
+    kept iff floor(rand_k + 1 - p) = 1, the draws from the CPU generator; kept values are
+    scaled by 1 / (1 - p). keep_mask(nnz) is the draw alone (NGCF applies it to its CSR
+    values, in that order)."""
+
+    def __init__(self, p=0.5):
+        super().__init__()
+        self.kprob = 1 - p
+
+    def keep_mask(self, nnz):
+        return (torch.rand(nnz) + self.kprob).floor().type(torch.bool)
+
+    def forward(self, x):
+        if not self.training:
+            return x
+        x = x.coalesce() if not x.is_coalesced() else x
+        mask = self.keep_mask(x._values().size(0)).to(x.device)
+        return torch.sparse_coo_tensor(x._indices()[:, mask], x._values()[mask] * (1.0 / self.kprob),
+                                       x.shape)
+
+
+NGCF_SITE = 0x4000                            # + layer: K16a's message dropout (0x3000: K15a)

@@ -1421,10 +1421,19 @@ class SpmmPlan:
 
 
 def spmm_csr(plan: SpmmPlan, x, y=None, add=None, add_scale: float = 1.0, acc_in=None,
-             acc_out=None, acc_scale: float = 1.0):
+             acc_out=None, acc_scale: float = 1.0, vals=None):
     """One K7 launch: y = A @ x (+ add_scale*add); Y = y; ACC_OUT = (ACC_IN + y)*acc_scale.
-    Each operand is None, a [n, d] tensor or a (lo, hi) pair of row blocks."""
+    Each operand is None, a [n, d] tensor or a (lo, hi) pair of row blocks. vals: other
+    values for the plan's pattern ([nnz] float32 in the plan's entry order; default
+    plan.vals)."""
     from recbole_amd._native import SpmmEpilogue
+    if vals is None:
+        vals = plan.vals
+    else:
+        _dev(vals, torch.float32, "vals")
+        if vals.shape != plan.vals.shape:
+            raise ValueError(f"spmm_csr: vals shape {tuple(vals.shape)} != "
+                             f"{tuple(plan.vals.shape)}")
     n, d = _rows_n(x)
     if n != plan.n_rows:
         raise ValueError(f"spmm_csr: x has {n} rows, the matrix {plan.n_rows}")
@@ -1438,7 +1447,7 @@ def spmm_csr(plan: SpmmPlan, x, y=None, add=None, add_scale: float = 1.0, acc_in
     ep = SpmmEpilogue(_rows_ref(add), add_scale, _rows_ref(y), _rows_ref(acc_in),
                       _rows_ref(acc_out), acc_scale)
     xr = _rows_ref(x)
-    rc = lib().mirec_spmm_csr_f32(ptr(plan.row_ptr), ptr(plan.cols), ptr(plan.vals), plan.n_rows,
+    rc = lib().mirec_spmm_csr_f32(ptr(plan.row_ptr), ptr(plan.cols), ptr(vals), plan.n_rows,
                                   d, ptr(plan.unit_row), ptr(plan.unit_beg), ptr(plan.unit_slot),
                                   plan.n_units, plan.piece, ptr(plan.fix_row), ptr(plan.fix_ptr),
                                   plan.n_fix, ptr(part), ctypes.byref(xr), ctypes.byref(ep),
@@ -1470,3 +1479,149 @@ def gather_scale_rows(table, idx, scale_dev, out=None):
                                            stream_handle())
     check(rc, "mirec_gather_scale_rows_f32")
     return out
+
+
+# ---------------------------------------------------------------- K16 NGCF bi-interaction
+def _rows_ld(t, d: int, name: str):
+    """(mirec_rows_ld, n rows) from None, a [n, d] float32 GPU tensor whose rows are
+    contiguous (a column slice of a wider row-major buffer is fine) or a (lo, hi) pair of
+    such blocks with one row stride."""
+    from recbole_amd._native import RowsLd
+    if t is None:
+        return RowsLd(None, None, 0, 0), 0
+    parts = t if isinstance(t, tuple) else (t,)
+    for p in parts:
+        if not isinstance(p, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor or a pair of them")
+        if not p.is_cuda:
+            raise NativeError(f"{name} must live on the GPU (got {p.device}); no CPU fallback "
+                              f"exists")
+        if p.dtype != torch.float32 or p.dim() != 2 or p.shape[1] != d:
+            raise ValueError(f"{name} must be float32 [n, {d}], got {p.dtype} {tuple(p.shape)}")
+        if p.stride(1) != 1 or p.stride(0) < d or p.stride(0) % 4 or p.data_ptr() % 16:
+            raise ValueError(f"{name}: rows must be contiguous, 16-byte aligned, with a row "
+                             f"stride that is a multiple of 4")
+    if len(parts) == 2:
+        lo, hi = parts
+        if lo.stride(0) != hi.stride(0):
+            raise ValueError(f"{name}: the two row blocks have different row strides")
+        return RowsLd(ptr(lo), ptr(hi), lo.shape[0], lo.stride(0)), lo.shape[0] + hi.shape[0]
+    return RowsLd(ptr(t), None, t.shape[0], t.stride(0)), t.shape[0]
+
+
+def ngcf_shape_ok(d_in: int, d_out: int) -> bool:
+    """Whether K16 is built for a layer d_in -> d_out ({64, 128}^2)."""
+    return lib().mirec_ngcf_shape_ok(int(d_in), int(d_out)) != 0
+
+
+def ngcf_grid_cap(workgroups: int) -> int:
+    """Cap the workgroups of K16a / K16b at `workgroups` (0: the chip decides; negative: only
+    ask); returns the cap before the call. No output bit depends on it: the tests use it to
+    make every wave walk many slabs at a small N."""
+    return int(lib().mirec_ngcf_grid_cap(int(workgroups)))
+
+
+def _ngcf_widths(what, W1, W2, b1=None, b2=None):
+    _dev(W1, torch.float32, "W1")
+    _dev(W2, torch.float32, "W2")
+    d_out, d_in = W1.shape
+    if W2.shape != W1.shape:
+        raise ValueError(f"{what}: W1 {tuple(W1.shape)} and W2 {tuple(W2.shape)} differ")
+    if not ngcf_shape_ok(d_in, d_out):
+        raise NativeError(f"{what}: widths {d_in} -> {d_out} not in the built set ({{64,128}}^2)")
+    for n_, b in (("b1", b1), ("b2", b2)):
+        if b is not None:
+            _dev(b, torch.float32, n_)
+            if b.shape != (d_out,):
+                raise ValueError(f"{what}: {n_} shape {tuple(b.shape)} != ({d_out},)")
+    return d_in, d_out
+
+
+def ngcf_layer_fwd(E, x, W1, b1, W2, b2, out, copy=None, p: float = 0.0, rng=None, drawn=None):
+    """K16a: out = normalize(dropout_p(leaky_relu_0.2((E + x) W1^T + b1 + (x * E) W2^T + b2)))
+    per row, written into `out` (a rows operand: typically a column slice of the [N, D]
+    concat buffer) and optionally `copy` (contiguous [N, d_out]); returns nrm [N] = the row
+    norms before the scale. E: a rows operand ([N, d_in] or the (user, item) table pair).
+    p > 0: rng = (seed, device int64 counter), drawn = a device int64 word that takes the
+    counter value used (the counter is advanced by the backward)."""
+    d_in, d_out = _ngcf_widths("ngcf_layer_fwd", W1, W2, b1, b2)
+    _dev(x, torch.float32, "x")
+    Er, n = _rows_ld(E, d_in, "E")
+    Or, n_o = _rows_ld(out, d_out, "out")
+    if x.shape != (n, d_in) or n_o != n:
+        raise ValueError(f"ngcf_layer_fwd: E has {n} rows, x {tuple(x.shape)}, out {n_o} rows")
+    if copy is not None:
+        _dev(copy, torch.float32, "copy")
+        if copy.shape != (n, d_out):
+            raise ValueError(f"ngcf_layer_fwd: copy shape {tuple(copy.shape)} != {(n, d_out)}")
+    nrm = torch.empty(n, dtype=torch.float32, device=x.device)
+    seed, counter = (0, None) if not p else rng
+    if p:
+        _dev(counter, torch.int64, "counter")
+        _dev(drawn, torch.int64, "drawn")
+    rc = lib().mirec_ngcf_layer_fwd_f32(ctypes.byref(Er), ptr(x), n, d_in, d_out, ptr(W1), ptr(b1),
+                                        ptr(W2), ptr(b2), ctypes.byref(Or), ptr(copy), ptr(nrm),
+                                        float(p), seed, ptr(counter), ptr(drawn) if p else None,
+                                        stream_handle())
+    check(rc, "mirec_ngcf_layer_fwd_f32")
+    return nrm
+
+
+def ngcf_layer_bwd(G, E_next, nrm, W1, W2, E, x, add=None, p: float = 0.0, rng=None, drawn=None):
+    """K16b: from G (the gradient of a layer's output E_next, both rows operands) returns
+    (gz [N, d_out], dE [N, d_in] = g_z W1 + (g_z W2) * x (+ add), gx [N, d_in] =
+    g_z W1 + (g_z W2) * E); the layer's input gradient is A'^T gx + dE. p > 0 redraws the
+    forward's keep bits from `drawn` and sets the counter of rng to drawn + 1."""
+    d_in, d_out = _ngcf_widths("ngcf_layer_bwd", W1, W2)
+    _dev(x, torch.float32, "x")
+    _dev(nrm, torch.float32, "nrm")
+    Gr, n = _rows_ld(G, d_out, "G")
+    Nr, n_n = _rows_ld(E_next, d_out, "E_next")
+    Er, n_e = _rows_ld(E, d_in, "E")
+    Ar, n_a = _rows_ld(add, d_in, "add")
+    if not (n_n == n_e == n) or x.shape != (n, d_in) or nrm.shape != (n,) or \
+            (add is not None and n_a != n):
+        raise ValueError("ngcf_layer_bwd: operands disagree on the number of rows")
+    dev = x.device
+    gz = torch.empty(n, d_out, dtype=torch.float32, device=dev)
+    dE = torch.empty(n, d_in, dtype=torch.float32, device=dev)
+    gx = torch.empty(n, d_in, dtype=torch.float32, device=dev)
+    seed, counter = (0, None) if not p else rng
+    if p:
+        _dev(counter, torch.int64, "counter")
+        _dev(drawn, torch.int64, "drawn")
+    rc = lib().mirec_ngcf_layer_bwd_f32(ctypes.byref(Gr), ctypes.byref(Nr), ptr(nrm), n, d_in,
+                                        d_out, ptr(W1), ptr(W2), ctypes.byref(Er), ptr(x),
+                                        ctypes.byref(Ar), ptr(gz), ptr(dE), ptr(gx), float(p),
+                                        seed, ptr(drawn) if p else None, ptr(counter),
+                                        stream_handle())
+    check(rc, "mirec_ngcf_layer_bwd_f32")
+    return gz, dE, gx
+
+
+def ngcf_wgrad(gz, E, x, d_in: int):
+    """K16c + the finish: (dW1, dW2 [d_out, d_in], db [d_out]) = g_z^T (E + x), g_z^T (x * E)
+    and the column sum of g_z, over the node rows in a fixed order."""
+    _dev(gz, torch.float32, "gz")
+    _dev(x, torch.float32, "x")
+    n, d_out = gz.shape
+    if not ngcf_shape_ok(d_in, d_out):
+        raise NativeError(f"ngcf_wgrad: widths {d_in} -> {d_out} not in the built set "
+                          f"({{64,128}}^2)")
+    Er, n_e = _rows_ld(E, d_in, "E")
+    if n_e != n or x.shape != (n, d_in) or n == 0:
+        raise ValueError("ngcf_wgrad: operands disagree on the number of rows")
+    dev = gz.device
+    C = lib().mirec_ngcf_wgrad_splits(n)
+    P = torch.empty(C, d_out, 2 * d_in, dtype=torch.float32, device=dev)
+    check(lib().mirec_ngcf_wgrad_f32(ptr(gz), ctypes.byref(Er), ptr(x), n, d_in, d_out, ptr(P),
+                                     stream_handle()), "mirec_ngcf_wgrad_f32")
+    dW = torch.empty(d_out, 2 * d_in, dtype=torch.float32, device=dev)
+    db = torch.empty(d_out, dtype=torch.float32, device=dev)
+    scratch = torch.empty(max(lib().mirec_linear_grad_finish_scratch(n, d_out), 2),
+                          dtype=torch.float32, device=dev)
+    check(lib().mirec_linear_grad_finish_f32(ptr(P), C, d_out * 2 * d_in, ptr(dW), ptr(gz), n,
+                                             d_out, ptr(db), ptr(scratch),
+                                             ptr(finish_ticket(dev, 'linear')), stream_handle()),
+          "mirec_linear_grad_finish_f32")
+    return dW[:, :d_in].contiguous(), dW[:, d_in:].contiguous(), db

@@ -29,6 +29,12 @@ C2 headline (bench.py): one JSON line per configuration, 1 GPU.
       statement of the reference's step on the same device, weights and batches (ms/step,
       users/s, peak allocated), and the full-sort evaluation, fused (K15d) against the
       generic sequence on a user subset. Not in the default list: --configs A2.
+  G2  NGCF on C5's graph generator at --scale (widths 64 / [64, 64, 64], message dropout
+      0.1, B = 2,048 BPR triples): one training step on K7 + K16 + K3 against a torch
+      statement of the same step (torch.sparse.mm, Linear, leaky_relu, dropout, normalize,
+      cat, gathers) on the same device, weights and batches: ms/step and peak allocated of
+      both over alternating timed windows, and the two steps' loss and gradients compared
+      with the dropout off. Not in the default list: --configs G2.
 
 Synthetic data (seeded numpy PCG64 / torch generators), random init. Each step is
 the Trainer's generic step: zero_grad -> calculate_loss -> backward -> FusedAdam.
@@ -1003,6 +1009,125 @@ def bench_c5(dev, scale=1.0, d=256, n_layers=2, K=10, sample_users=131072):
     }
 
 
+# ----------------------------------------------------------------------------- G2
+def bench_ngcf(dev, steps, warmup, scale=1.0, B=2048, windows=3):
+    """One NGCF training step (zero_grad, calculate_loss, backward, FusedAdam) on
+    make_c5_graph at `scale`, widths 64 / [64, 64, 64], message dropout 0.1: the model's
+    kernel path against the torch op sequence written below, on copies of the same initial
+    weights and the same batches. `windows` timed windows of `steps` steps each, the two
+    sides alternating; peak allocated memory of each side's windows. Before the timing the
+    two steps' loss and gradients are compared on the first batch with the dropout off (the
+    two sides draw their masks from different generators)."""
+    import copy
+    import scipy.sparse as sp
+    import torch.nn.functional as F
+    from recbole_amd.config import Config
+    from recbole_amd.data.interaction import Interaction
+    from recbole_amd.model.general_recommender import NGCF
+    from recbole_amd.trainer.optim import FusedAdam
+    from recbole_amd.utils import FeatureType
+    U, I = int(10_000_000 * scale) + 1, int(5_000_000 * scale) + 1
+    t0 = time.perf_counter()
+    u, i = make_c5_graph(U - 1, I - 1, int(100_000_000 * scale))
+
+    class _Graph(StubDataset):
+        def inter_matrix(self, form='coo'):
+            return sp.coo_matrix((np.ones(len(u), dtype=np.float32), (u, i)), shape=(U, I))
+
+    config = Config(model='NGCF', dataset='c5-synth', config_dict={
+        'state': 'ERROR', 'data_path': ROOT, 'load_col': None})
+    config['device'] = dev
+    torch.manual_seed(2020)
+    model = NGCF(config, _Graph({'user_id': FeatureType.TOKEN, 'item_id': FeatureType.TOKEN},
+                                {'user_id': U, 'item_id': I})).to(dev)
+    assert model._kernel_path() and list(model.hidden_size_list) == [64, 64, 64, 64]
+    twin = copy.deepcopy(model)                       # the torch statement's weights
+    A = model._torch_matrix(None, dev).coalesce()
+    model.norm_adj_plan                               # the K7 plan, outside the timing
+    setup = time.perf_counter() - t0
+    rng = np.random.default_rng(2020)
+    batches = []
+    for _ in range(8):
+        e = rng.integers(0, len(u), B)
+        batches.append(Interaction({'user_id': torch.as_tensor(u[e]),
+                                    'item_id': torch.as_tensor(i[e]),
+                                    'neg_item_id': torch.as_tensor(rng.integers(1, I, B))}).to(dev))
+
+    def torch_loss(m, b, p):
+        E = torch.cat([m.user_embedding.weight, m.item_embedding.weight], dim=0)
+        out = [E]
+        for g in m.GNNlayers:
+            x = torch.sparse.mm(A, E)
+            z = g.linear(E + x) + g.interActTransform(x * E)
+            E = F.normalize(F.dropout(F.leaky_relu(z, 0.2), p, True), p=2, dim=1)
+            out.append(E)
+        ua, ia = torch.split(torch.cat(out, dim=1), [U, I])
+        a, ps, ng = ua[b['user_id']], ia[b['item_id']], ia[b['neg_item_id']]
+        mf = -torch.log(1e-10 + torch.sigmoid((a * ps).sum(1) - (a * ng).sum(1))).mean()
+        return mf + m.reg_weight * (a.norm() + ps.norm() + ng.norm()) / a.shape[0]
+
+    # the two steps' outputs on the first timed batch, dropout off
+    model.message_dropout = 0.0
+    lk = model.calculate_loss(batches[0])
+    lk.backward()
+    lt = torch_loss(twin, batches[0], 0.0)
+    lt.backward()
+    check = {'loss_kernels': lk.item(), 'loss_torch': lt.item(),
+             'loss_rel_diff': abs(lk.item() - lt.item()) / abs(lt.item()), 'grad_max_abs_diff': {},
+             'grad_max_abs_torch': {}}
+    for (name, a), (_, b) in zip(model.named_parameters(), twin.named_parameters()):
+        check['grad_max_abs_diff'][name] = float((a.grad - b.grad).abs().max())
+        check['grad_max_abs_torch'][name] = float(b.grad.abs().max())
+    model.zero_grad(set_to_none=True)
+    twin.zero_grad(set_to_none=True)
+    model.message_dropout = 0.1
+
+    opt_k = FusedAdam(model.parameters(), lr=1e-3)
+    opt_t = FusedAdam(twin.parameters(), lr=1e-3)
+    it = [0, 0]
+
+    def step_k():
+        b = batches[it[0] % len(batches)]
+        it[0] += 1
+        opt_k.zero_grad()
+        model.calculate_loss(b).backward()
+        opt_k.step()
+
+    def step_t():
+        b = batches[it[1] % len(batches)]
+        it[1] += 1
+        opt_t.zero_grad()
+        torch_loss(twin, b, 0.1).backward()
+        opt_t.step()
+
+    tk, tt, peak = [], [], [0, 0]
+    for w in range(windows):
+        for side, (fn, ts) in enumerate(((step_k, tk), (step_t, tt))):
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats(dev)
+            ts.append(_timed(fn, steps, warmup if w == 0 else 1))
+            peak[side] = max(peak[side], torch.cuda.max_memory_allocated(dev))
+    mk, mt = float(np.median(tk)), float(np.median(tt))
+    return {
+        'config': 'G2', 'model': 'NGCF', 'metric': 'train steps/s', 'value': round(1 / mk, 2),
+        'unit': 'steps/s', 'ms_per_step': round(mk * 1e3, 3),
+        'ms_per_step_windows': [round(t * 1e3, 3) for t in tk],
+        'torch': {'ms_per_step': round(mt * 1e3, 3),
+                  'ms_per_step_windows': [round(t * 1e3, 3) for t in tt],
+                  'peak_allocated_MB': round(peak[1] / 1e6, 1)},
+        'speedup_vs_torch': round(mt / mk, 2),
+        'peak_allocated_MB': round(peak[0] / 1e6, 1),
+        'windows': windows, 'steps': steps, 'batch': B, 'graph_step': False,
+        'outputs_dropout_off': check,
+        'workload': f'NGCF {U - 1:,} users x {I - 1:,} items, {len(u):,} edges (scale {scale}), '
+                    f'64 / [64, 64, 64], message dropout 0.1, BPR + EmbLoss, FusedAdam',
+        'dtype': 'fp32', 'data': 'synthetic (Zipf items, Zipf-like user degrees, seeded)',
+        'setup_s': round(setup, 1),
+        'note': f'first measurement: {windows} alternating windows of {steps} steps in one '
+                f'process; no repeat across processes, spread beyond the windows not measured',
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--configs', default='C3,C4,C5')
@@ -1038,6 +1163,8 @@ def main():
             r = bench_neumf(dev, args.steps, args.warmup, args.scale)
         elif c == 'A2':
             r = bench_multivae(dev, args.steps, args.warmup, args.scale)
+        elif c == 'G2':
+            r = bench_ngcf(dev, args.steps, args.warmup, args.scale)
         else:
             raise SystemExit(f'unknown config {c}')
         print(json.dumps(r), flush=True)
