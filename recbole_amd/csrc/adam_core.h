@@ -229,9 +229,9 @@ __device__ __forceinline__ float div_bc2s_finite(float x, const StepConsts& sc) 
 }
 
 // Increments q = RN(RN(-ss*me) / den), den = RN(RN(sqrt(ve) / bc2s) + eps), of G
-// consecutive zero-gradient steps x N elements. The fast path is computed for all
-// G*N first and one wave vote on its range conditions decides (a branch per step
-// would serialise the steps' chains); the library path recomputes everything.
+// consecutive zero-gradient steps x N elements. One wave vote on the fast path's range
+// conditions decides for all G*N (a branch per step would serialise the steps' chains);
+// the library path recomputes everything.
 // The range conditions are tested at the group's first and last step only: over
 // consecutive zero-gradient steps ve (= RN(ve * b2)), |me| (= RN(me * (1-b1)),
 // lerp_small), step_size (host table, non-increasing: FusedAdam.step_constants
@@ -241,17 +241,29 @@ __device__ __forceinline__ float div_bc2s_finite(float x, const StepConsts& sc) 
 // The fast-path increments two at a time on gfx950's packed fp32 pipe (v_pk_fma_f32 /
 // v_pk_mul_f32 / v_pk_add_f32: two IEEE fp32 operations per lane and instruction, each
 // rounded as its scalar form), for G*N independent (step, element) pairs. Same operations,
-// same roundings, same order per value as sqrt_rn_normal / div_bc2s_finite / div_rn_normal.
+// same roundings, same order per value as sqrt_rn_fast / div_bc2s_finite / div_rn_normal.
 typedef float mirec_f2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ mirec_f2 pk_fma(mirec_f2 a, mirec_f2 b, mirec_f2 c) {
   return __builtin_elementwise_fma(a, b, c);
 }
 
-// q = RN(RN(-ss*me) / den), den = RN(RN(RN(sqrt(ve)) / bc2s) + eps), for two pairs at once
-// (each pair with its own step constants)
-__device__ __forceinline__ mirec_f2 incr_pair(mirec_f2 me, mirec_f2 ve, mirec_f2 ss,
-                                              mirec_f2 bc2s, mirec_f2 rbc, float eps) {
+// den = RN(RN(RN(sqrt(ve)) / bc2s) + eps) for two (step, element) pairs at once, each with
+// its own step constants
+__device__ __forceinline__ mirec_f2 den_pair(mirec_f2 ve, mirec_f2 bc2s, mirec_f2 rbc,
+                                             float eps) {
+#if !defined(MIREC_SQRT_ULP_FIXUP)
+  // sqrt_rn_normal_rsq: one v_rsq_f32 per element, the rest packed
+  const mirec_f2 half = {0.5f, 0.5f};
+  const mirec_f2 ry = {__builtin_amdgcn_rsqf(ve.x), __builtin_amdgcn_rsqf(ve.y)};
+  const mirec_f2 g0 = ve * ry;
+  const mirec_f2 h0 = half * ry;
+  const mirec_f2 rr = pk_fma(-h0, g0, half);
+  const mirec_f2 g1 = pk_fma(g0, rr, g0);
+  const mirec_f2 h1 = pk_fma(h0, rr, h0);
+  const mirec_f2 dd = pk_fma(-g1, g1, ve);
+  const mirec_f2 sq = pk_fma(dd, h1, g1);
+#else
   // sqrt_rn_normal, component-wise selects
   const mirec_f2 s = {__builtin_amdgcn_sqrtf(ve.x), __builtin_amdgcn_sqrtf(ve.y)};
   const mirec_f2 sd = {__uint_as_float(__float_as_uint(s.x) - 1u),
@@ -263,11 +275,14 @@ __device__ __forceinline__ mirec_f2 incr_pair(mirec_f2 me, mirec_f2 ve, mirec_f2
   mirec_f2 sq;
   sq.x = ru.x > 0.f ? su.x : (rd.x <= 0.f ? sd.x : s.x);
   sq.y = ru.y > 0.f ? su.y : (rd.y <= 0.f ? sd.y : s.y);
+#endif
   // div_bc2s_finite + eps
   const mirec_f2 q = sq * rbc;
-  const mirec_f2 den = pk_fma(pk_fma(-q, bc2s, sq), rbc, q) + (mirec_f2){eps, eps};
-  // div_rn_normal(-ss * me, den)
-  const mirec_f2 a = (-ss) * me;
+  return pk_fma(pk_fma(-q, bc2s, sq), rbc, q) + (mirec_f2){eps, eps};
+}
+
+// div_rn_normal(a, den) for two pairs at once
+__device__ __forceinline__ mirec_f2 quot_pair(mirec_f2 a, mirec_f2 den) {
   const mirec_f2 y0 = {__builtin_amdgcn_rcpf(den.x), __builtin_amdgcn_rcpf(den.y)};
   const mirec_f2 one = {1.0f, 1.0f};
   const mirec_f2 e = pk_fma(-den, y0, one);
@@ -283,56 +298,81 @@ template <int G, int N>
 __device__ __forceinline__ void incr_steps(const float (*me)[N], const float (*ve)[N],
                                            const StepConsts* sc, const AdamConsts& k,
                                            float (*q)[N]) {
-  float num[G][N], den[G][N];
-  // range conditions at the group's first and last step (see below); the values they
-  // test are recomputed in the paired path exactly as here
+  constexpr int NE = G * N;
+  int ok = 1;                                   // int: no short-circuit branches
+  // the range conditions of element (j, i) of the group: those of the first step at
+  // j == 0, those of the last at j == G - 1 (both for a group of one step)
+  auto range_ok = [&](int j, float ve_, float num_, float den_) {
+    int r = 1;
+    if (j == 0)
+      r &= (int)(ve_ <= 0x1.fffffep127f) & (int)(fabsf(num_) <= 0x1p40f) &
+           (int)(den_ <= 0x1p40f);
+    if (j == G - 1)
+      r &= (int)(ve_ >= 0x1p-96f) & (int)(fabsf(num_) >= 0x1p-60f) & (int)(den_ >= 0x1p-40f);
+    return r;
+  };
+#if defined(MIREC_NO_PK)                        // probe build: the scalar form
 #pragma unroll
   for (int j = 0; j < G; j += (G > 1 ? G - 1 : 1))
 #pragma unroll
-    for (int i = 0; i < N; ++i) {
-      den[j][i] = div_bc2s_finite(sqrt_rn_normal(ve[j][i]), sc[j]) + k.eps;
-      num[j][i] = (-sc[j].ss) * me[j][i];
-    }
-  int ok = 1;                                   // int: no short-circuit branches
-#pragma unroll
-  for (int i = 0; i < N; ++i)
-    ok &= (int)(ve[0][i] <= 0x1.fffffep127f) & (int)(ve[G - 1][i] >= 0x1p-96f) &
-          (int)(fabsf(num[0][i]) <= 0x1p40f) & (int)(fabsf(num[G - 1][i]) >= 0x1p-60f) &
-          (int)(den[0][i] <= 0x1p40f) & (int)(den[G - 1][i] >= 0x1p-40f);
+    for (int i = 0; i < N; ++i)
+      ok &= range_ok(j, ve[j][i], (-sc[j].ss) * me[j][i],
+                     div_bc2s_finite(sqrt_rn_fast(ve[j][i]), sc[j]) + k.eps);
   if (__all(ok)) {
-    constexpr int NE = G * N;
-#if defined(MIREC_NO_PK)                        // probe build: the scalar form
 #pragma unroll
     for (int e = 0; e < NE; ++e) {
       const int j = e / N, i = e % N;
       q[j][i] = div_rn_normal((-sc[j].ss) * me[j][i],
-                              div_bc2s_finite(sqrt_rn_normal(ve[j][i]), sc[j]) + k.eps);
+                              div_bc2s_finite(sqrt_rn_fast(ve[j][i]), sc[j]) + k.eps);
     }
     return;
-#endif
+  }
+#else
+  // Pairs of consecutive (step, element) values. The pairs that hold a value of the
+  // group's first or last step get their numerator and denominator before the vote,
+  // which tests them; the fast path goes on from these and forms the other pairs only
+  // then (nothing of the tested pairs is computed twice).
+  constexpr int NP = NE / 2;
+  auto at_end = [](int e) { return e / N == 0 || e / N == G - 1; };
+  mirec_f2 nump[NP > 0 ? NP : 1], denp[NP > 0 ? NP : 1];
+  auto form = [&](int e) {
+    const int ja = e / N, ia = e % N, jb = (e + 1) / N, ib = (e + 1) % N;
+    nump[e / 2] = -(mirec_f2){sc[ja].ss, sc[jb].ss} * (mirec_f2){me[ja][ia], me[jb][ib]};
+    denp[e / 2] = den_pair((mirec_f2){ve[ja][ia], ve[jb][ib]},
+                           (mirec_f2){sc[ja].bc2s, sc[jb].bc2s},
+                           (mirec_f2){sc[ja].rbc, sc[jb].rbc}, k.eps);
+  };
+#pragma unroll
+  for (int e = 0; e + 1 < NE; e += 2)
+    if (at_end(e) || at_end(e + 1)) {
+      form(e);
+      ok &= range_ok(e / N, ve[e / N][e % N], nump[e / 2].x, denp[e / 2].x) &
+            range_ok((e + 1) / N, ve[(e + 1) / N][(e + 1) % N], nump[e / 2].y, denp[e / 2].y);
+    }
+  constexpr int jl = (NE - 1) / N, il = (NE - 1) % N;   // an odd count: the last one alone
+  float numl = 0.f, denl = 1.f;                 // (always a value of the last step)
+  if (NE & 1) {
+    numl = (-sc[jl].ss) * me[jl][il];
+    denl = div_bc2s_finite(sqrt_rn_fast(ve[jl][il]), sc[jl]) + k.eps;
+    ok &= range_ok(jl, ve[jl][il], numl, denl);
+  }
+  if (__all(ok)) {
 #pragma unroll
     for (int e = 0; e + 1 < NE; e += 2) {
-      const int ja = e / N, ia = e % N, jb = (e + 1) / N, ib = (e + 1) % N;
-      const mirec_f2 r = incr_pair((mirec_f2){me[ja][ia], me[jb][ib]},
-                                   (mirec_f2){ve[ja][ia], ve[jb][ib]},
-                                   (mirec_f2){sc[ja].ss, sc[jb].ss},
-                                   (mirec_f2){sc[ja].bc2s, sc[jb].bc2s},
-                                   (mirec_f2){sc[ja].rbc, sc[jb].rbc}, k.eps);
-      q[ja][ia] = r.x;
-      q[jb][ib] = r.y;
+      if (!(at_end(e) || at_end(e + 1))) form(e);
+      const mirec_f2 r = quot_pair(nump[e / 2], denp[e / 2]);
+      q[e / N][e % N] = r.x;
+      q[(e + 1) / N][(e + 1) % N] = r.y;
     }
-    if (NE & 1) {                               // an odd count: the last one alone
-      constexpr int jl = (NE - 1) / N, il = (NE - 1) % N;
-      const float dl = div_bc2s_finite(sqrt_rn_normal(ve[jl][il]), sc[jl]) + k.eps;
-      q[jl][il] = div_rn_normal((-sc[jl].ss) * me[jl][il], dl);
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < G; ++j)
-#pragma unroll
-      for (int i = 0; i < N; ++i)
-        q[j][i] = ((-sc[j].ss) * me[j][i]) / (div_bc2s(sqrtf(ve[j][i]), sc[j]) + k.eps);
+    if (NE & 1) q[jl][il] = div_rn_normal(numl, denl);
+    return;
   }
+#endif
+#pragma unroll
+  for (int j = 0; j < G; ++j)
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+      q[j][i] = ((-sc[j].ss) * me[j][i]) / (div_bc2s(sqrtf(ve[j][i]), sc[j]) + k.eps);
 }
 
 // ---- replay of a row that fills whole waves (s0 wave-uniform); the fast-path
@@ -349,11 +389,21 @@ __device__ __forceinline__ void incr_steps(const float (*me)[N], const float (*v
 // additions to p in step order — the same operations and roundings as one step
 // at a time. While every element's p update provably rounds away
 // (p_update_vanishes; p is then fixed, so its exponent part is computed once)
-// a group only moves m and v. The test runs at the first step of every group
-// outside that state (as adam_replay's every 4th step); a group whose four steps
-// do not all pass goes step by step. Full steps use the fast-path sqrt /
-// division of adam_math.h. G = steps per group (8: eight chains in flight for a
-// thread holding one element).
+// a group only moves m and v. Outside that state the test runs at the first step
+// of the call's first group (a row that arrives already vanishing is caught at
+// once) and then of every kVanishEvery-th group: a skipped step gives exactly the
+// bits of the full step, so how often a wave that is not skipping looks is free,
+// and the price is entering the state up to (kVanishEvery - 1) * G steps late,
+// once per idle period of a row. A group whose first step passes and whose steps
+// do not all pass goes step by step. Full steps use the fast-path sqrt / division
+// of adam_math.h. G = steps per group (8: eight chains in flight for a thread
+// holding one element).
+#if !defined(MIREC_VANISH_EVERY)
+#define MIREC_VANISH_EVERY 4                    // 1: the test at every group
+#endif
+constexpr int kVanishEvery = MIREC_VANISH_EVERY;
+static_assert(kVanishEvery >= 1 && (kVanishEvery & (kVanishEvery - 1)) == 0,
+              "MIREC_VANISH_EVERY: a power of two");
 template <typename V, int G = 4>
 __device__ __forceinline__ void adam_replay_row(V& p, V& m, V& v, int s0, int s1,
                                                 const float* __restrict__ consts,
@@ -422,7 +472,7 @@ __device__ __forceinline__ void adam_replay_row(V& p, V& m, V& v, int s0, int s1
 
   // (loading the next group's step constants under this group's arithmetic was
   // measured slower: the scalar-load wait covers both groups' loads)
-  for (; s + G <= s1; s += G) {
+  for (int gi = 0; s + G <= s1; s += G, ++gi) {
     StepConsts sc[G];
 #pragma unroll
     for (int j = 0; j < G; ++j) sc[j] = step_consts(consts, s + j);
@@ -447,11 +497,15 @@ __device__ __forceinline__ void adam_replay_row(V& p, V& m, V& v, int s0, int s1
       group_done = __all(mine);                 // four skipped steps
       if (group_done) MIREC_WORK(1, G * N * MIREC_WORK_LANES());
     } else {
-      bool mine = true;
+      bool first_vanishes = false;
+      if (kVanishEvery == 1 || (gi & (kVanishEvery - 1)) == 0) {
+        bool mine = true;
 #pragma unroll
-      for (int i = 0; i < N; ++i)
-        mine = mine && p_update_vanishes(pc[i], me[0][i], ve[0][i], sc[0], k.eps);
-      if (!__all(mine)) {                       // four full steps, increments side by side
+        for (int i = 0; i < N; ++i)
+          mine = mine && p_update_vanishes(pc[i], me[0][i], ve[0][i], sc[0], k.eps);
+        first_vanishes = __all(mine);
+      }
+      if (!first_vanishes) {                    // four full steps, increments side by side
         float q[G][N];
         incr_steps<G, N>(me, ve, sc, k, q);
         MIREC_WORK(0, G * N * MIREC_WORK_LANES());

@@ -28,6 +28,38 @@ __device__ __forceinline__ float sqrt_rn_normal(float x) {
   return ru > 0.f ? su : r;
 }
 
+// The same value from v_rsq_f32 and fma alone: the refinement of the compiler's
+// correctly rounded sqrt expansion for flushed denormals (one coupled
+// Newton-Raphson step of g ~ sqrt(x), h ~ 1/(2 sqrt(x)), then the residual x - g*g
+// folded in), without its input scaling and 0 / inf fix-up. No integer ulp
+// neighbours, compares or selects, and every operation has a packed form
+// (incr_pair in adam_core.h). The fma forms x - g*g in full, so g*g near FLT_MAX
+// does not overflow. That the result is the correctly rounded one for EVERY float
+// of [2^-96, FLT_MAX] on this GPU's v_rsq_f32 is checked, not argued: sqrt takes
+// one fp32 argument, and mirec_selftest_adam_math with sqrt_stride = 1 compares
+// them all with sqrtf (tests/test_gpu_replay_diet.py).
+__device__ __forceinline__ float sqrt_rn_normal_rsq(float x) {
+  const float y = __builtin_amdgcn_rsqf(x);
+  float g = x * y;
+  float h = 0.5f * y;
+  const float r = fmaf(-h, g, 0.5f);
+  g = fmaf(g, r, g);
+  h = fmaf(h, r, h);
+  const float d = fmaf(-g, g, x);
+  return fmaf(d, h, g);
+}
+
+// The sqrt the replay's fast path calls (adam_core.h: incr_steps, and incr_pair's
+// packed restatement). -DMIREC_SQRT_ULP_FIXUP: the v_sqrt_f32 + ulp fix-up form,
+// to measure the two against each other; same bits either way.
+__device__ __forceinline__ float sqrt_rn_fast(float x) {
+#if defined(MIREC_SQRT_ULP_FIXUP)
+  return sqrt_rn_normal(x);
+#else
+  return sqrt_rn_normal_rsq(x);
+#endif
+}
+
 __device__ __forceinline__ bool sqrt_fast_ok(float x) {
   return x >= 0x1p-96f && x <= 0x1.fffffep127f;
 }
