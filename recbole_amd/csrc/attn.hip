@@ -16,22 +16,20 @@
 //             through the dropout), then all waves take 16-row strips of
 //             dQ = dS K / sqrt(dh), dK = dS^T Q / sqrt(dh), dV = P'^T dO.
 //
-// Dropout draws are counter-based: key = splitmix64(splitmix64(seed) ^ c), c the forward's
-// counter value (the seed and the counter enter separately: under seed + c a module at step
-// t + 1 drew the mask of the module with the next seed at step t; numpy restatement in
-// tests/drop_spec.py); for a row i = 16w + 4lk + r with r even and a column j, one draw
-// x = splitmix64(key ^ (((b H + h) 64 + i) 64 + j)) decides element (i, j) by its low 32
-// bits and element (i + 1, j) by its high 32 bits (kept iff < thr);
+// Dropout draws use drop.h's key and threshold (numpy restatement: tests/drop_spec.py
+// attn_keep), with K9e's own element indexing: for a row i = 16w + 4lk + r with r even and a
+// column j, one draw x = mix64(key ^ (((b H + h) 64 + i) 64 + j)) decides element (i, j) by
+// its low 32 bits and element (i + 1, j) by its high 32 bits (kept iff < thr);
 // the keep bits are saved as the forward's ballot words (64 per (b, h): wave w, column
 // tile c, row r -> word (w 4 + c) 4 + r, bit li + 16 lk for row 16w + 4lk + r, column
 // 16c + li) and read back by the backward, which advances the device counter by one store
 // (captured steps draw new masks every replay; a last-block ticket in the forward serialised
 // 4,096 atomics on one word, ~11 us a launch).
 #include "common.h"
+#include "drop.h"
+#include "mfma.h"
 
 namespace mirec {
-
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 // exp / log / the softmax's division in their hardware forms (v_exp_f32, v_log_f32, one
 // reciprocal per row: a few ulp, inside the path's 1e-4 tolerance; fwd 71 -> 66 us at C3's
@@ -74,17 +72,6 @@ struct AttnArgs {
   uint64_t seed;
   int64_t* counter;     // forward: read; backward: advanced (one store)
 };
-
-__device__ __forceinline__ uint64_t at_mix(uint64_t z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-__device__ __forceinline__ floatx4 at_mfma(float a, float b, floatx4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
 
 // Tiles of rows 0..63 of one head's [L, 64] slice (row stride ld floats; rows >= L zero):
 // at_load issues every float4 load of NT tiles into registers, at_store writes them to LDS
@@ -142,16 +129,16 @@ __device__ __forceinline__ void at_abt(floatx4 (&acc)[4], const float4 (&a)[4],
     // order
 #pragma unroll
     for (int c = 0; c < 4; ++c)
-      if ((live >> c) & 1u) acc[c] = at_mfma(a[u].x, b[c].x, acc[c]);
+      if ((live >> c) & 1u) acc[c] = mfma_16x16x4(a[u].x, b[c].x, acc[c]);
 #pragma unroll
     for (int c = 0; c < 4; ++c)
-      if ((live >> c) & 1u) acc[c] = at_mfma(a[u].y, b[c].y, acc[c]);
+      if ((live >> c) & 1u) acc[c] = mfma_16x16x4(a[u].y, b[c].y, acc[c]);
 #pragma unroll
     for (int c = 0; c < 4; ++c)
-      if ((live >> c) & 1u) acc[c] = at_mfma(a[u].z, b[c].z, acc[c]);
+      if ((live >> c) & 1u) acc[c] = mfma_16x16x4(a[u].z, b[c].z, acc[c]);
 #pragma unroll
     for (int c = 0; c < 4; ++c)
-      if ((live >> c) & 1u) acc[c] = at_mfma(a[u].w, b[c].w, acc[c]);
+      if ((live >> c) & 1u) acc[c] = mfma_16x16x4(a[u].w, b[c].w, acc[c]);
   }
 }
 
@@ -170,7 +157,7 @@ __device__ __forceinline__ void at_ab(floatx4 (&acc)[4], const float (*A)[kAtLd]
       const int k = 16 * u + 4 * lk + e;
       const float ae = e == 0 ? a.x : e == 1 ? a.y : e == 2 ? a.z : a.w;
 #pragma unroll
-      for (int c = 0; c < 4; ++c) acc[c] = at_mfma(ae, Bm[k][16 * c + li], acc[c]);
+      for (int c = 0; c < 4; ++c) acc[c] = mfma_16x16x4(ae, Bm[k][16 * c + li], acc[c]);
     }
   }
 }
@@ -190,7 +177,7 @@ __device__ __forceinline__ void at_atb(floatx4 (&acc)[4], const float (*At)[kAtL
       const int k = 16 * u + 4 * lk + e;
       const float a = At[k][j0 + li];
 #pragma unroll
-      for (int c = 0; c < 4; ++c) acc[c] = at_mfma(a, Bm[k][16 * c + li], acc[c]);
+      for (int c = 0; c < 4; ++c) acc[c] = mfma_16x16x4(a, Bm[k][16 * c + li], acc[c]);
     }
   }
 }
@@ -208,7 +195,8 @@ __global__ __launch_bounds__(kAtThreads) void attn_fwd_kernel(AttnArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 15, lk = lane >> 4;
   const int64_t base = b * L * ld + h * kAtD;
   const bool drop = a.keep != nullptr;
-  const uint64_t key = drop ? at_mix(at_mix(a.seed) ^ (uint64_t)a.counter[0]) : 0ull;
+  // drop.h's drop_key, written out
+  const uint64_t key = drop ? mix64(mix64(a.seed) ^ (uint64_t)a.counter[0]) : 0ull;
   {
     float4 kv[2][kAtPer];
     const float* const srcs[2] = {a.k + base, a.v + base};
@@ -275,7 +263,7 @@ __global__ __launch_bounds__(kAtThreads) void attn_fwd_kernel(AttnArgs a) {
       uint64_t d = 0ull;
       if (drop) {
         const int row = 16 * w + 4 * lk + r, col = 16 * c + li;
-        d = at_mix(key ^ (((uint64_t)bh * kAtL + row) * kAtL + col));
+        d = mix64(key ^ (((uint64_t)bh * kAtL + row) * kAtL + col));
       }
 #pragma unroll
       for (int h2 = 0; h2 < 2; ++h2) {
@@ -484,7 +472,7 @@ extern "C" int mirec_attn_fwd_f32(const float* q, const float* k, const float* v
       return -1;
     }
     a.keep = keep_words;
-    a.keep_thr = (uint32_t)fmin(4294967295.0, ldexp(1.0 - (double)dropout_p, 32));
+    a.keep_thr = drop_threshold(dropout_p);
     a.keep_scale = 1.0f / (1.0f - dropout_p);
     a.seed = seed;
     a.counter = counter;

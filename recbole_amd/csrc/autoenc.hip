@@ -17,7 +17,8 @@
 //   per lane for N = 1024), FOUR rows in flight, adding them item after item. A round is 4
 //   units (one per wave); after each round the 4 partial sums go through LDS and thread t
 //   adds them to its total in unit order: total = (((total + u0) + u1) + u2) + u3. So
-//   y[b] = act(bias + c_b * total) is one fixed sum whatever the row length.
+//   y[b] = act(bias + c_b * total) is one fixed sum whatever the row length. The keep flag
+//   is drop.h's draw of element e = b * n_items + item.
 // K15b bag_expand_kernel: one wave per batch row writes the row's (item, b, weight)
 //   triples at off[b]..; the draw is the forward's (same key, same element index).
 //   bag_bwd_chunk_kernel: one wave per kBagChunk = 32 sorted positions (K2's chunk). Lane j
@@ -54,6 +55,8 @@
 //   nll_fwd_kernel 24 / 32        nll_bwd_kernel 45 / 16
 //   matrix_topk_kernel<10 / 20 / 50>  38 / 58 / 119 VGPRs, 32 B of LDS (K <= 50 moves 40
 //   SGPRs into VGPR lanes)
+#include "common.h"
+#include "drop.h"
 #include "topk.h"
 
 namespace mirec {
@@ -63,23 +66,6 @@ constexpr int kBagSplit = MIREC_BAG_ROW_SPLIT;
 constexpr int kBagChunk = MIREC_BAG_SEG_CHUNK;
 static_assert(kBagSplit == 64, "a unit is one item per lane");
 static_assert(kBagChunk <= 62, "a chunk is one position per lane; lanes 62 / 63 fetch its edges");
-
-__device__ __forceinline__ uint64_t bag_mix(uint64_t z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-__device__ __forceinline__ uint64_t bag_key(uint64_t seed, int64_t c) {
-  return bag_mix(bag_mix(seed) ^ (uint64_t)c);
-}
-
-// keep flag of element e = b * n_items + item
-__device__ __forceinline__ bool bag_keep(uint64_t key, uint64_t e, uint32_t thr) {
-  const uint64_t h = bag_mix(key ^ (e >> 1));
-  return ((e & 1) ? (uint32_t)(h >> 32) : (uint32_t)h) < thr;
-}
 
 __device__ __forceinline__ float4 f4add(float4 a, float4 b) {
   return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
@@ -116,7 +102,7 @@ __global__ __launch_bounds__(kBagThreads) void bag_fwd_kernel(
   uint64_t key = 0;
   if (DROP) {
     const int64_t cv = counter[0];
-    key = bag_key(seed, cv);
+    key = drop_key(seed, cv);
     if (b == 0 && tid == 0) drawn[0] = cv;
   }
   const float4* __restrict__ W4 = reinterpret_cast<const float4*>(Wt);
@@ -127,7 +113,7 @@ __global__ __launch_bounds__(kBagThreads) void bag_fwd_kernel(
     int item = -1;
     if (j < nb) item = hcols[a + j];
     bool ok = item >= 0 && (int64_t)item < n_items;
-    if (DROP && ok) ok = bag_keep(key, (uint64_t)b * (uint64_t)n_items + (uint64_t)item, thr);
+    if (DROP && ok) ok = drop_keep(key, (uint64_t)b * (uint64_t)n_items + (uint64_t)item, thr);
     unsigned long long mask = __ballot(ok);
     float4 acc[V];
 #pragma unroll
@@ -197,7 +183,7 @@ __global__ __launch_bounds__(kBagThreads) void bag_expand_kernel(
   uint64_t key = 0;
   if (DROP) {
     const int64_t cv = drawn[0];
-    key = bag_key(seed, cv);
+    key = drop_key(seed, cv);
     if (blockIdx.x == 0 && threadIdx.x == 0) counter[0] = cv + 1;      // the next draw
   }
   if (b >= B) return;
@@ -212,7 +198,7 @@ __global__ __launch_bounds__(kBagThreads) void bag_expand_kernel(
     if (q < 0 || q >= nnz) continue;                 // off disagrees with the CSR: write nothing
     const int item = hcols[a + j];
     bool ok = item >= 0 && (int64_t)item < n_items;
-    if (DROP && ok) ok = bag_keep(key, (uint64_t)b * (uint64_t)n_items + (uint64_t)item, thr);
+    if (DROP && ok) ok = drop_keep(key, (uint64_t)b * (uint64_t)n_items + (uint64_t)item, thr);
     keys[q] = item >= 0 && (int64_t)item < n_items ? (int64_t)item : 0;
     row_of[q] = (int32_t)b;
     wgt[q] = ok ? cb : 0.f;
@@ -600,11 +586,6 @@ __global__ __launch_bounds__(kMtThreads) void matrix_topk_kernel(
   }
 }
 
-static uint32_t bag_threshold(float p) {
-  const double t = ldexp(1.0 - (double)p, 32);
-  return t >= 4294967295.0 ? 4294967295u : (uint32_t)t;
-}
-
 static bool bag_width_ok(int32_t N) { return N >= 4 && N <= 1024 && N % 4 == 0; }
 
 }  // namespace mirec
@@ -637,7 +618,7 @@ extern "C" int mirec_bag_linear_fwd_f32(const int64_t* users, int64_t B, const i
     return -1;
   }
   const int n4 = N / 4;
-  const uint32_t thr = drop ? bag_threshold(p) : 0u;
+  const uint32_t thr = drop ? drop_threshold(p) : 0u;
   const float inv_keep = drop ? 1.0f / (1.0f - p) : 1.0f;
   hipStream_t st = (hipStream_t)stream;
 #define MIREC_CALL(VV)                                                                          \
@@ -669,7 +650,7 @@ extern "C" int mirec_bag_expand_f32(const int64_t* users, int64_t B, const int64
               "0 < p < 1 with the counter and the drawn word)");
     return -1;
   }
-  const uint32_t thr = drop ? bag_threshold(p) : 0u;
+  const uint32_t thr = drop ? drop_threshold(p) : 0u;
   const float inv_keep = drop ? 1.0f / (1.0f - p) : 1.0f;
   const int rpb = kBagThreads / 64;
   const dim3 grid((unsigned)((B + rpb - 1) / rpb));

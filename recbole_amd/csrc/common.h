@@ -22,6 +22,57 @@ inline int launch_status(const char* what) {
   return hip_status(hipGetLastError(), what);
 }
 
+// Per-device launch facts (CU count; per kernel the workgroups a CU holds), cached by device
+// index. Callers hold the interpreter lock; two host threads racing here would store the same
+// values twice. A device index past the table is looked up on every launch.
+constexpr int kMaxDev = 16;
+
+inline int current_device() {
+  int dev = -1;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) return -1;
+  return dev;
+}
+
+inline int device_cus(int dev) {
+  static int cache[kMaxDev] = {};
+  if (dev >= 0 && cache[dev]) return cache[dev];
+  int cus = 256, d = dev;
+  if (d >= 0 || hipGetDevice(&d) == hipSuccess)
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, d);
+  if (dev >= 0) cache[dev] = cus;
+  return cus;
+}
+
+// First launch of a kernel on a device: allow its dynamic LDS there and, where per_cu is
+// asked for, find how many of its workgroups a CU holds (registers and LDS decide), 1 .. 4:
+// a persistent grid is that many workgroups per CU. `cache` is the kernel's own table (one
+// static per instantiation).
+template <typename Kern>
+int prepare_launch(Kern kern, int threads, size_t lds, int (&cache)[kMaxDev], int* per_cu,
+                   const char* what) {
+  const int dev = current_device();
+  if (dev >= 0 && cache[dev]) {
+    if (per_cu) *per_cu = cache[dev];
+    return 0;
+  }
+  const int rc = hip_status(
+      hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
+      what);
+  if (rc) return rc;
+  int n = 1;
+  if (per_cu) {
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)kern, threads, lds) !=
+        hipSuccess) {
+      (void)hipGetLastError();
+      n = 1;
+    }
+    n = n < 1 ? 1 : (n > 4 ? 4 : n);
+    *per_cu = n;
+  }
+  if (dev >= 0) cache[dev] = n;
+  return 0;
+}
+
 constexpr int kWave = 64;
 
 __device__ __forceinline__ float wave_sum(float x) {

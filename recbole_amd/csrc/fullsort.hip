@@ -26,11 +26,11 @@
 // is permuted (k = 4*(s>>1) + 2h + (s&1)) so both operands load as float2; the
 // MFMA result is an exact-f32 fma chain in that order.
 #include "common.h"
+#include "mfma.h"
 #include "topk.h"   // topk_insert / topk_merge_insert, hist_lower_bound
 
 namespace mirec {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 constexpr int kFsThreads = 256;
 
@@ -206,8 +206,8 @@ __global__ __launch_bounds__(kFsThreads, MIREC_FS_WAVES_PER_EU(D)) void fullsort
 #pragma unroll
       for (int s2 = 0; s2 < D / 4; ++s2) {
         const float2 a = *reinterpret_cast<const float2*>(arow + 4 * s2);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, ub[2 * s2], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, ub[2 * s2 + 1], acc, 0, 0, 0);
+        acc = mfma_32x32x2(a.x, ub[2 * s2], acc);
+        acc = mfma_32x32x2(a.y, ub[2 * s2 + 1], acc);
       }
       // Rows of this lane that can enter its list: valid item, not pad, not history.
       // C[item row][user col]: rows (r&3) + 8*(r>>2) + 4h
@@ -351,8 +351,8 @@ __global__ __launch_bounds__(kFsThreads) void score_matrix_kernel(const float* _
 #pragma unroll
     for (int s2 = 0; s2 < D / 4; ++s2) {
       const float2 b = *reinterpret_cast<const float2*>(brow + 4 * s2);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ub[2 * s2], b.x, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ub[2 * s2 + 1], b.y, acc, 0, 0, 0);
+      acc = mfma_32x32x2(ub[2 * s2], b.x, acc);
+      acc = mfma_32x32x2(ub[2 * s2 + 1], b.y, acc);
     }
     const int64_t item = base + j;
 #pragma unroll

@@ -16,22 +16,17 @@
 // The weight gradient (dW = dY^T X over the 10^5 rows) stays the split-K batched product
 // + mirec_linear_grad_finish_f32.
 #include "common.h"
+#include "mfma.h"
 
 #include <algorithm>
 
 namespace mirec {
-
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 #ifndef MIREC_LN_GW
 #define MIREC_LN_GW 4
 #endif
 constexpr int kLnThreads = 512;           // eight waves
 constexpr int kLnWaves = kLnThreads / 64;
-
-__device__ __forceinline__ floatx4 ln_mfma(float a, float b, floatx4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
 
 // Y[M, N] = X[M, K] B[K, N] (+ bias), B[k][n] = WT ? W[k][n] : W[n][k] (W row-major). One
 // workgroup per CU stages the whole weight once; each of its waves then walks 16-row slabs
@@ -91,41 +86,7 @@ __global__ __launch_bounds__(kLnThreads) void linear_mfma_kernel(
     float4 an[kPre ? NU : 1];
     if (kPre) load_a(reinterpret_cast<float4(&)[NU]>(an), s + nw);   // next slab, in flight
     floatx4 acc[NC];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) acc[c] = floatx4{0.f, 0.f, 0.f, 0.f};
-    // groups g = (k slice u, GW column tiles cg..): the next group's B reads are issued
-    // before this group's MFMAs (their LDS latency under the products); GW accumulators
-    // interleaved, so a dependent MFMA follows its predecessor GW issues later
-    constexpr int GW = NC < MIREC_LN_GW ? NC : MIREC_LN_GW;
-    constexpr int NG = NU * (NC / GW);
-    auto load_b = [&](float4 (&b)[GW], int g) {
-      const int u = g / (NC / GW), cg = GW * (g % (NC / GW));
-#pragma unroll
-      for (int c = 0; c < GW; ++c)
-        b[c] = *reinterpret_cast<const float4*>(&Bs[(16 * (cg + c) + li) * KP + 16 * u + 4 * lk]);
-    };
-    float4 bc[GW];
-    load_b(bc, 0);
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      const int u = g / (NC / GW), cg = GW * (g % (NC / GW));
-      float4 bn[GW];
-      if (g + 1 < NG) load_b(bn, g + 1);
-      __builtin_amdgcn_sched_barrier(0);   // the reads stay ahead of this group's MFMAs
-#pragma unroll
-      for (int c = 0; c < GW; ++c) acc[cg + c] = ln_mfma(a[u].x, bc[c].x, acc[cg + c]);
-#pragma unroll
-      for (int c = 0; c < GW; ++c) acc[cg + c] = ln_mfma(a[u].y, bc[c].y, acc[cg + c]);
-#pragma unroll
-      for (int c = 0; c < GW; ++c) acc[cg + c] = ln_mfma(a[u].z, bc[c].z, acc[cg + c]);
-#pragma unroll
-      for (int c = 0; c < GW; ++c) acc[cg + c] = ln_mfma(a[u].w, bc[c].w, acc[cg + c]);
-      // the scheduler keeps this order (no hoisting of later groups' reads)
-      __builtin_amdgcn_sched_barrier(0);
-      if (g + 1 < NG)
-#pragma unroll
-        for (int c = 0; c < GW; ++c) bc[c] = bn[c];
-    }
+    mfma_slab<NU, NC, KP, MIREC_LN_GW>(a, lds_ptr(Bs), li, lk, acc);
     // C layout: acc[c][i] = Y[16 s + 4lk + i][16c + li]
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -150,22 +111,11 @@ template <int K, int N, bool WT, bool ACC>
 int launch_linear(const float* X, int64_t M, const float* W, const float* bias, const float* R,
                   float* Y, hipStream_t st, const char* what) {
   constexpr size_t lds = (size_t)N * (K + 4) * sizeof(float);
-  static bool attr = false;
-  if (!attr) {
-    if (hip_status(hipFuncSetAttribute((const void*)linear_mfma_kernel<K, N, WT, ACC>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-                   what))
-      return -1;
-    attr = true;
-  }
+  static int cache[kMaxDev] = {};
+  if (prepare_launch(linear_mfma_kernel<K, N, WT, ACC>, kLnThreads, lds, cache, nullptr, what))
+    return -1;
   const int per_cu = 1;   // eight waves per CU (the VGPR budget of the wider forms: 2 per SIMD)
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess)
-      (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  }
+  const int cus = device_cus(current_device());
   const int64_t slabs = (M + 15) / 16;
   const int64_t grid = std::min<int64_t>((slabs + kLnWaves - 1) / kLnWaves, (int64_t)cus * per_cu);
   hipLaunchKernelGGL((linear_mfma_kernel<K, N, WT, ACC>), dim3((unsigned)grid), dim3(kLnThreads),

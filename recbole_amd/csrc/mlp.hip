@@ -22,10 +22,13 @@
 //
 // Dropout draws are counter-based (mirec_mlp_draw below; restated in numpy by
 // tests/mlp_spec.py): element e of layer l in the forward with counter value c is
-// kept iff  splitmix64(splitmix64(seed + c) ^ (e * 8 + l)) >> 32  <  keep_threshold.
+// kept iff  mix64(mix64(seed + c) ^ (e * 8 + l)) >> 32  <  keep_threshold  (drop.h's mix64;
+// the key and the element word are K10's older rule, not drop.h's drop_key / drop_keep).
 // The counter lives on the device and the last block of each training forward
 // advances it, so captured steps (HIP graph replays) draw new masks every step.
 #include "common.h"
+#include "drop.h"
+#include "mfma.h"
 
 #include <cstdlib>
 
@@ -40,21 +43,8 @@ constexpr int kMlpU = 4;           // 16-wide slices per prefetch group (data gr
 #endif
 constexpr int kFwdU = MIREC_FWD_U; // forward: 8 slices (32 MFMAs) per group
 
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
 __device__ __forceinline__ bool mlp_keep(uint64_t key, int layer, uint64_t elem, uint32_t thr) {
-  return (uint32_t)(splitmix64(key ^ (elem * 8ull + (uint64_t)layer)) >> 32) < thr;
-}
-
-__device__ __forceinline__ floatx4 mfma4(float a, float b, floatx4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
+  return (uint32_t)(mix64(key ^ (elem * 8ull + (uint64_t)layer)) >> 32) < thr;
 }
 
 // Row strides (floats) of the two LDS tiles: widths dims[j] of even j live in tile A,
@@ -103,10 +93,10 @@ __device__ __forceinline__ floatx4 tile_dot(const float* cur, int ld, const floa
 #pragma unroll
     for (int u = 0; u < kFwdU; ++u) {
       floatx4& acc = (u & 1) ? accB : accA;
-      acc = mfma4(ca[u].x, cb[u].x, acc);
-      acc = mfma4(ca[u].y, cb[u].y, acc);
-      acc = mfma4(ca[u].z, cb[u].z, acc);
-      acc = mfma4(ca[u].w, cb[u].w, acc);
+      acc = mfma_16x16x4(ca[u].x, cb[u].x, acc);
+      acc = mfma_16x16x4(ca[u].y, cb[u].y, acc);
+      acc = mfma_16x16x4(ca[u].z, cb[u].z, acc);
+      acc = mfma_16x16x4(ca[u].w, cb[u].w, acc);
     }
   }
   return accA + accB;
@@ -186,7 +176,7 @@ __global__ __launch_bounds__(kMlpThreads * KS) void mlp_fwd_kernel(mirec_mlp a, 
   const int L = a.n_layers;
   bool any_drop = false;
   for (int l = 0; l < L; ++l) any_drop |= train && a.dropout[l];
-  const uint64_t key = any_drop ? splitmix64(a.seed + (uint64_t)a.counter[0]) : 0ull;
+  const uint64_t key = any_drop ? mix64(a.seed + (uint64_t)a.counter[0]) : 0ull;
 
   stage_rows<kMlpThreads * KS>(a, x, l0, B, r0, train && a.dropout[0], true, key,
                                (l0 & 1) ? tB : tA, (l0 & 1) ? ldB : ldA);
@@ -280,7 +270,7 @@ __global__ __launch_bounds__(kWideThreads) void mlp_l0_fwd_kernel(mirec_mlp a,
   const int K = a.dims[0], N = a.dims[1], L = a.n_layers;
   bool any_drop = false;
   for (int l = 0; l < L; ++l) any_drop |= train && a.dropout[l];
-  const uint64_t key = any_drop ? splitmix64(a.seed + (uint64_t)a.counter[0]) : 0ull;
+  const uint64_t key = any_drop ? mix64(a.seed + (uint64_t)a.counter[0]) : 0ull;
   stage_rows<kWideThreads>(a, x, 0, B, r0, train && a.dropout[0], blockIdx.y == 0, key, tA, ld);
   __syncthreads();
   const int nsl = (K + 15) / 16, half = (nsl + 1) / 2;
@@ -405,7 +395,7 @@ __global__ __launch_bounds__(kMlpThreads) void mlp_bwd_data_kernel(mirec_mlp a,
       for (int u = 0; u < kMlpU; ++u) {
         floatx4& acc = (u & 1) ? accB : accA;
 #pragma unroll
-        for (int s = 0; s < 4; ++s) acc = mfma4(ca[u][s], cb[u][s], acc);
+        for (int s = 0; s < 4; ++s) acc = mfma_16x16x4(ca[u][s], cb[u][s], acc);
       }
       if (it % ng != ng - 1) continue;
       // the tile is complete: epilogue
@@ -488,7 +478,7 @@ __global__ __launch_bounds__(kMlpThreads) void mlp_bwd_weight_kernel(mirec_mlp a
 #pragma unroll
     for (int s = 0; s < S; ++s) {
       floatx4& acc = (s & 1) ? accB : accA;
-      acc = mfma4(ca[s], cb[s], acc);
+      acc = mfma_16x16x4(ca[s], cb[s], acc);
       bsum += ca[s];
     }
   }
@@ -603,10 +593,10 @@ __global__ __launch_bounds__(kWideThreads) void mlp_bwd_wide_kernel(
       const float av[4] = {ca.x, ca.y, ca.z, ca.w};
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        acc[0] = mfma4(av[e], cbv[e].x, acc[0]);
-        acc[1] = mfma4(av[e], cbv[e].y, acc[1]);
-        acc[2] = mfma4(av[e], cbv[e].z, acc[2]);
-        acc[3] = mfma4(av[e], cbv[e].w, acc[3]);
+        acc[0] = mfma_16x16x4(av[e], cbv[e].x, acc[0]);
+        acc[1] = mfma_16x16x4(av[e], cbv[e].y, acc[1]);
+        acc[2] = mfma_16x16x4(av[e], cbv[e].z, acc[2]);
+        acc[3] = mfma_16x16x4(av[e], cbv[e].w, acc[3]);
       }
     }
     if (!cin) return;
@@ -671,10 +661,10 @@ __global__ __launch_bounds__(kWideThreads) void mlp_bwd_wide_kernel(
     if (b0 + 16 < b_hi) load(b0 + 16);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      acc[0] = mfma4(ca[e], cbv[e].x, acc[0]);
-      acc[1] = mfma4(ca[e], cbv[e].y, acc[1]);
-      acc[2] = mfma4(ca[e], cbv[e].z, acc[2]);
-      acc[3] = mfma4(ca[e], cbv[e].w, acc[3]);
+      acc[0] = mfma_16x16x4(ca[e], cbv[e].x, acc[0]);
+      acc[1] = mfma_16x16x4(ca[e], cbv[e].y, acc[1]);
+      acc[2] = mfma_16x16x4(ca[e], cbv[e].z, acc[2]);
+      acc[3] = mfma_16x16x4(ca[e], cbv[e].w, acc[3]);
       bsum += ca[e];
     }
   }

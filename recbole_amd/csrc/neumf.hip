@@ -19,11 +19,10 @@
 //       user into a register top-K behind the pad / history mask (K6's order: score desc,
 //       item id asc). No [users x items x anything] tensor exists in HBM.
 #include "common.h"
+#include "mfma.h"
 #include "topk.h"
 
 namespace mirec {
-
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 constexpr int kGatherThreads = 256;
 
@@ -178,9 +177,6 @@ struct PairCfg {
   int oW[4];
 };
 
-__device__ __forceinline__ floatx4 pmfma(float a, float b, floatx4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
 __device__ __forceinline__ float relu_f(float z) { return z < 0.f ? 0.f : z; }   // NaN passes
 
 // The wave's LDS rows written by some lanes are read by others: order them.
@@ -233,14 +229,14 @@ __device__ __forceinline__ void pair_layer(const float* W, int ldw, const float*
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         if (j < nj) {                              // wave-uniform
-          acc[0][j] = pmfma(x0.x, w[j].x, acc[0][j]);
-          acc[1][j] = pmfma(x1.x, w[j].x, acc[1][j]);
-          acc[0][j] = pmfma(x0.y, w[j].y, acc[0][j]);
-          acc[1][j] = pmfma(x1.y, w[j].y, acc[1][j]);
-          acc[0][j] = pmfma(x0.z, w[j].z, acc[0][j]);
-          acc[1][j] = pmfma(x1.z, w[j].z, acc[1][j]);
-          acc[0][j] = pmfma(x0.w, w[j].w, acc[0][j]);
-          acc[1][j] = pmfma(x1.w, w[j].w, acc[1][j]);
+          acc[0][j] = mfma_16x16x4(x0.x, w[j].x, acc[0][j]);
+          acc[1][j] = mfma_16x16x4(x1.x, w[j].x, acc[1][j]);
+          acc[0][j] = mfma_16x16x4(x0.y, w[j].y, acc[0][j]);
+          acc[1][j] = mfma_16x16x4(x1.y, w[j].y, acc[1][j]);
+          acc[0][j] = mfma_16x16x4(x0.z, w[j].z, acc[0][j]);
+          acc[1][j] = mfma_16x16x4(x1.z, w[j].z, acc[1][j]);
+          acc[0][j] = mfma_16x16x4(x0.w, w[j].w, acc[0][j]);
+          acc[1][j] = mfma_16x16x4(x1.w, w[j].w, acc[1][j]);
         }
       }
     }
@@ -493,13 +489,11 @@ static int pair_launch(const mirec_pair_mlp& m, const PairCfg& c, size_t shm, in
                        int K, float* top_scores, int32_t* top_ids, uint8_t* pos_flags, float* S,
                        hipStream_t st) {
   auto kern = pair_mlp_kernel<KC, SCORES, WLDS>;
-  if (shm > 64 * 1024) {
-    const int rc = hip_status(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                  (int)shm),
-                              "mirec_pair_mlp: LDS size attribute");
-    if (rc) return rc;
-  }
+  // shm varies with the layer widths: allow the most any descriptor is given
+  static int cache[kMaxDev] = {};
+  const int rc = prepare_launch(kern, 64 * NW, kPairLdsMax, cache, nullptr,
+                                "mirec_pair_mlp: LDS size attribute");
+  if (rc) return rc;
   hipLaunchKernelGGL(kern, dim3((unsigned)((nq + kPairTU - 1) / kPairTU)), dim3(64 * NW), shm, st,
                      m, c, A, Pq, nq, Bm, I_mf, I, hist_ptr, hist_cols, pos_ptr, pos_cols, K,
                      top_scores, top_ids, pos_flags, S);

@@ -30,11 +30,7 @@
 // values, so all lanes hold the same bits) after the column tiles in tile order, the
 // K16c rows in row order. No float atomics.
 //
-// Message dropout: K9d's counter-based draws (seq.hip, tests/drop_spec.py ln_keep):
-// key = mix(mix(seed) ^ c), element e = row * d_out + column takes half e & 1 of
-// mix(key ^ (e >> 1)), keep iff that 32-bit draw < thr. The forward reads the device
-// counter c and records it in drawn[0]; the backward redraws from drawn[0] and sets the
-// counter to drawn[0] + 1.
+// Message dropout: the shared counter-based draw (drop.h), element e = row * d_out + column.
 //
 // Rows operands are (lo, hi, split, ld): row r at lo + r ld below split, else at
 // hi + (r - split) ld — the two embedding tables as E_0, a column slice of the concat
@@ -49,16 +45,15 @@
 //   (128, 128)      178 / 252, 133120 B            168 / 168, 135168 B           122
 // (K16c uses no LDS; eight waves a workgroup leave each wave 256 registers.)
 #include "common.h"
+#include "drop.h"
+#include "mfma.h"
 
 #include <algorithm>
 
 namespace mirec {
 
-typedef float nfloatx4 __attribute__((ext_vector_type(4)));
-
 constexpr int kNgThreads = 512;           // eight waves
 constexpr int kNgWaves = kNgThreads / 64;
-constexpr int kNgGW = 4;                  // accumulators interleaved per group (as K11)
 
 struct RowsLd {
   float* lo;
@@ -70,78 +65,12 @@ struct RowsLd {
   }
 };
 
-struct NgDrop {
-  uint32_t thr;
-  float scale;
-  uint64_t seed;
-  int64_t* counter;
-  int64_t* drawn;
-};
-
-__device__ __forceinline__ nfloatx4 ng_mfma(float a, float b, nfloatx4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ uint64_t ng_mix(uint64_t z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-__device__ __forceinline__ uint64_t ng_key(uint64_t seed, int64_t c) {
-  return ng_mix(ng_mix(seed) ^ (uint64_t)c);
-}
-
-__device__ __forceinline__ bool ng_keep(uint64_t key, uint64_t e, uint32_t thr) {
-  const uint64_t h = ng_mix(key ^ (e >> 1));
-  return ((e & 1) ? (uint32_t)(h >> 32) : (uint32_t)h) < thr;
-}
-
-// the products of one slab: acc[c] += A[:, 16u..] Bs[16c.., 16u..]^T over every k slice u,
-// B reads one group ahead of the MFMAs (K11's loop)
-template <int NU, int NC, int KP>
-__device__ __forceinline__ void ng_slab(const float4 (&a)[NU], const float* Bs, int li, int lk,
-                                        nfloatx4 (&acc)[NC]) {
-  constexpr int GW = NC < kNgGW ? NC : kNgGW;
-  constexpr int NG = NU * (NC / GW);
-#pragma unroll
-  for (int c = 0; c < NC; ++c) acc[c] = nfloatx4{0.f, 0.f, 0.f, 0.f};
-  auto load_b = [&](float4 (&b)[GW], int g) {
-    const int u = g / (NC / GW), cg = GW * (g % (NC / GW));
-#pragma unroll
-    for (int c = 0; c < GW; ++c)
-      b[c] = *reinterpret_cast<const float4*>(&Bs[(16 * (cg + c) + li) * KP + 16 * u + 4 * lk]);
-  };
-  float4 bc[GW];
-  load_b(bc, 0);
-#pragma unroll
-  for (int g = 0; g < NG; ++g) {
-    const int u = g / (NC / GW), cg = GW * (g % (NC / GW));
-    float4 bn[GW];
-    if (g + 1 < NG) load_b(bn, g + 1);
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int c = 0; c < GW; ++c) acc[cg + c] = ng_mfma(a[u].x, bc[c].x, acc[cg + c]);
-#pragma unroll
-    for (int c = 0; c < GW; ++c) acc[cg + c] = ng_mfma(a[u].y, bc[c].y, acc[cg + c]);
-#pragma unroll
-    for (int c = 0; c < GW; ++c) acc[cg + c] = ng_mfma(a[u].z, bc[c].z, acc[cg + c]);
-#pragma unroll
-    for (int c = 0; c < GW; ++c) acc[cg + c] = ng_mfma(a[u].w, bc[c].w, acc[cg + c]);
-    __builtin_amdgcn_sched_barrier(0);
-    if (g + 1 < NG)
-#pragma unroll
-      for (int c = 0; c < GW; ++c) bc[c] = bn[c];
-  }
-}
-
 // ---------------------------------------------------------------- K16a
 template <int DI, int DO, bool DROP>
 __global__ __launch_bounds__(kNgThreads) void ngcf_fwd_kernel(
     const RowsLd E, const float* __restrict__ X, int64_t M, const float* __restrict__ W1,
     const float* __restrict__ b1, const float* __restrict__ W2, const float* __restrict__ b2,
-    const RowsLd out, float* __restrict__ copy, float* __restrict__ nrm, const NgDrop dr) {
+    const RowsLd out, float* __restrict__ copy, float* __restrict__ nrm, const DropSite dr) {
   constexpr int K = 2 * DI, KP = K + 4, NU = K / 16, NH = DI / 16, NC = DO / 16;
   extern __shared__ __attribute__((aligned(16))) float Bs[];   // [DO][KP]
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 15, lk = lane >> 4;
@@ -178,7 +107,7 @@ __global__ __launch_bounds__(kNgThreads) void ngcf_fwd_kernel(
   if (DROP) {
     const int64_t cv = dr.counter[0];
     if (blockIdx.x == 0 && tid == 0) dr.drawn[0] = cv;
-    key = ng_key(dr.seed, cv);
+    key = drop_key(dr.seed, cv);
   }
   __syncthreads();
 
@@ -186,8 +115,8 @@ __global__ __launch_bounds__(kNgThreads) void ngcf_fwd_kernel(
     constexpr bool kPre = NU <= 8;        // d_in = 128: no room for a second A slab
     float4 an[NU];                        // the next slab's A rows (kPre only; unused otherwise)
     if constexpr (kPre) load_a(an, s + nw);
-    nfloatx4 acc[NC];
-    ng_slab<NU, NC, KP>(a, Bs, li, lk, acc);
+    floatx4 acc[NC];
+    mfma_slab<NU, NC, KP>(a, Bs, li, lk, acc);
     // C layout: acc[c][i] = z[16 s + 4lk + i][16c + li] (before the bias)
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -199,7 +128,7 @@ __global__ __launch_bounds__(kNgThreads) void ngcf_fwd_kernel(
         const float z = acc[c][i] + bv[c];
         float h = z > 0.f ? z : 0.2f * z;
         if (DROP)
-          h = ng_keep(key, (uint64_t)r * DO + 16 * c + li, dr.thr) ? h * dr.scale : 0.f;
+          h = drop_keep(key, (uint64_t)r * DO + 16 * c + li, dr.thr) ? h * dr.scale : 0.f;
         m[c] = h;
         ss = fmaf(h, h, ss);
       }
@@ -233,7 +162,7 @@ __global__ __launch_bounds__(kNgThreads) void ngcf_bwd_kernel(
     const RowsLd G, const RowsLd En, const float* __restrict__ nrm, int64_t M,
     const float* __restrict__ W1, const float* __restrict__ W2, const RowsLd El,
     const float* __restrict__ X, const RowsLd add, float* __restrict__ gz,
-    float* __restrict__ dE, float* __restrict__ gx, const NgDrop dr) {
+    float* __restrict__ dE, float* __restrict__ gx, const DropSite dr) {
   constexpr int KP = DO + 4, NU = DO / 16, NC = 2 * DI / 16, NH = DI / 16;
   extern __shared__ __attribute__((aligned(16))) float Bs[];   // [2 DI][KP]
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 15, lk = lane >> 4;
@@ -255,7 +184,7 @@ __global__ __launch_bounds__(kNgThreads) void ngcf_bwd_kernel(
   if (DROP) {
     const int64_t cv = dr.drawn[0];
     if (blockIdx.x == 0 && tid == 0) dr.counter[0] = cv + 1;
-    key = ng_key(dr.seed, cv);
+    key = drop_key(dr.seed, cv);
   }
   __syncthreads();
 
@@ -293,14 +222,7 @@ __global__ __launch_bounds__(kNgThreads) void ngcf_bwd_kernel(
 #pragma unroll
       for (int u = 0; u < NU; ++u) {
         bool kp[4] = {true, true, true, true};
-        if (DROP) {
-          const uint64_t e0 = (uint64_t)r * DO + 16 * u + 4 * lk;
-          const uint64_t h0 = ng_mix(key ^ (e0 >> 1)), h1 = ng_mix(key ^ ((e0 >> 1) + 1));
-          kp[0] = (uint32_t)h0 < dr.thr;
-          kp[1] = (uint32_t)(h0 >> 32) < dr.thr;
-          kp[2] = (uint32_t)h1 < dr.thr;
-          kp[3] = (uint32_t)(h1 >> 32) < dr.thr;
-        }
+        if (DROP) drop_keep4(key, (uint64_t)r * DO + 16 * u + 4 * lk, dr.thr, kp);
         const float sc = DROP ? dr.scale : 1.f;
         auto one = [&](float gq, float eq, bool kq) {
           const float gm = (gq - eq * sd) / den;
@@ -311,8 +233,8 @@ __global__ __launch_bounds__(kNgThreads) void ngcf_bwd_kernel(
         if (ok) *reinterpret_cast<float4*>(gz + r * DO + 16 * u + 4 * lk) = a[u];
       }
     }
-    nfloatx4 acc[NC];
-    ng_slab<NU, NC, KP>(a, Bs, li, lk, acc);
+    floatx4 acc[NC];
+    mfma_slab<NU, NC, KP>(a, Bs, li, lk, acc);
     // C layout: acc[c][i] = g_a[16 s + 4lk + i][16c + li] for c < NH, g_p for c - NH
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -347,11 +269,11 @@ __global__ __launch_bounds__(kNgThreads) void ngcf_wgrad_kernel(
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 15, lk = lane >> 4;
   const int64_t r_beg = (int64_t)blockIdx.x * rows_per_block;
   const int64_t r_end = std::min<int64_t>(M, r_beg + rows_per_block);
-  nfloatx4 acc[NN][JW];
+  floatx4 acc[NN][JW];
 #pragma unroll
   for (int n = 0; n < NN; ++n)
 #pragma unroll
-    for (int j = 0; j < JW; ++j) acc[n][j] = nfloatx4{0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < JW; ++j) acc[n][j] = floatx4{0.f, 0.f, 0.f, 0.f};
   for (int64_t r0 = r_beg; r0 < r_end; r0 += 16) {
     float av[4][NN], bv[4][JW];
 #pragma unroll
@@ -376,7 +298,7 @@ __global__ __launch_bounds__(kNgThreads) void ngcf_wgrad_kernel(
 #pragma unroll
       for (int n = 0; n < NN; ++n)
 #pragma unroll
-        for (int j = 0; j < JW; ++j) acc[n][j] = ng_mfma(av[q][n], bv[q][j], acc[n][j]);
+        for (int j = 0; j < JW; ++j) acc[n][j] = mfma_16x16x4(av[q][n], bv[q][j], acc[n][j]);
   }
   // C layout: acc[n][j][i] = P[16n + 4lk + i][16 (w JW + j) + li]
   float* Pb = P + (int64_t)blockIdx.x * DO * K2;
@@ -390,27 +312,6 @@ __global__ __launch_bounds__(kNgThreads) void ngcf_wgrad_kernel(
 }
 
 // ---------------------------------------------------------------- host side
-// Per-device launch facts (CU count; per kernel the workgroups a CU holds), cached by device
-// index. Callers hold the interpreter lock; two host threads racing here would store the same
-// values twice. A device index past the table is looked up on every launch.
-constexpr int kNgMaxDev = 16;
-
-static int ng_device() {
-  int dev = -1;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kNgMaxDev) return -1;
-  return dev;
-}
-
-static int ng_cus(int dev) {
-  static int cache[kNgMaxDev] = {};
-  if (dev >= 0 && cache[dev]) return cache[dev];
-  int cus = 256, d = dev;
-  if (d >= 0 || hipGetDevice(&d) == hipSuccess)
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, d);
-  if (dev >= 0) cache[dev] = cus;
-  return cus;
-}
-
 // mirec_ngcf_grid_cap: most workgroups K16a / K16b launch (0: the CUs decide). Rows do not
 // depend on which wave walks them, so a cap changes no bit of any output; the tests cap the
 // grid to make every wave walk several slabs at a small N.
@@ -419,7 +320,7 @@ static int g_ng_grid_cap = 0;
 static unsigned ng_grid(int64_t M, int per_cu) {
   const int64_t slabs = (M + 15) / 16;
   int64_t grid = std::min<int64_t>((slabs + kNgWaves - 1) / kNgWaves,
-                                   (int64_t)ng_cus(ng_device()) * per_cu);
+                                   (int64_t)device_cus(current_device()) * per_cu);
   if (g_ng_grid_cap > 0) grid = std::min<int64_t>(grid, g_ng_grid_cap);
   return (unsigned)grid;
 }
@@ -435,57 +336,25 @@ static bool ng_rows_ok(const mirec_rows_ld* a, int d) {
          ((uintptr_t)a->hi % 16) == 0 && (!a->hi || a->split >= 0);
 }
 
-static int ng_drop(float p, uint64_t seed, int64_t* counter, int64_t* drawn, NgDrop* dr,
+// p == 0: a zeroed site, no dropout (the DROP = false kernels never read it)
+static int ng_drop(float p, uint64_t seed, int64_t* counter, int64_t* drawn, DropSite* dr,
                    const char* what) {
   memset(dr, 0, sizeof(*dr));
   if (p == 0.f) return 0;
-  if (!(p > 0.f && p < 1.f) || !counter || !drawn) {
-    set_error("%s: dropout %g needs 0 <= p < 1, the counter and the drawn word", what, (double)p);
-    return -1;
-  }
-  const double t = ldexp(1.0 - (double)p, 32);
-  dr->thr = t >= 4294967295.0 ? 4294967295u : (uint32_t)t;
-  dr->scale = 1.f / (1.f - p);
-  dr->seed = seed;
-  dr->counter = counter;
-  dr->drawn = drawn;
-  return 0;
+  return drop_site(p, seed, counter, drawn, dr, what);
 }
 
-// First launch of a kernel on a device: allow its dynamic LDS there and ask how many of its
-// workgroups a CU holds (registers and LDS decide: two for the 64 -> 64 backward, one for the
-// wide forms); the persistent grid is that many workgroups per CU.
-template <typename Kern>
-static int ng_prepare(Kern kern, size_t lds, int (&cache)[kNgMaxDev], int* per_cu,
-                      const char* what) {
-  const int dev = ng_device();
-  if (dev >= 0 && cache[dev]) {
-    *per_cu = cache[dev];
-    return 0;
-  }
-  if (hip_status(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)lds),
-                 what))
-    return -1;
-  int n = 1;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)kern, kNgThreads, lds) !=
-      hipSuccess) {
-    (void)hipGetLastError();
-    n = 1;
-  }
-  *per_cu = std::min(std::max(n, 1), 4);
-  if (dev >= 0) cache[dev] = *per_cu;
-  return 0;
-}
-
+// K16a / K16b run persistent grids of as many workgroups as a CU holds (prepare_launch: two
+// for the 64 -> 64 backward, one for the wide forms).
 template <int DI, int DO, bool DROP>
 static int launch_fwd(const RowsLd& E, const float* x, int64_t M, const float* W1, const float* b1,
                       const float* W2, const float* b2, const RowsLd& out, float* copy, float* nrm,
-                      const NgDrop& dr, hipStream_t st, const char* what) {
+                      const DropSite& dr, hipStream_t st, const char* what) {
   constexpr size_t lds = (size_t)DO * (2 * DI + 4) * sizeof(float);
-  static int cache[kNgMaxDev] = {};
+  static int cache[kMaxDev] = {};
   int per_cu = 1;
-  if (ng_prepare(ngcf_fwd_kernel<DI, DO, DROP>, lds, cache, &per_cu, what)) return -1;
+  if (prepare_launch(ngcf_fwd_kernel<DI, DO, DROP>, kNgThreads, lds, cache, &per_cu, what))
+    return -1;
   hipLaunchKernelGGL((ngcf_fwd_kernel<DI, DO, DROP>), dim3(ng_grid(M, per_cu)), dim3(kNgThreads), lds, st,
                      E, x, M, W1, b1, W2, b2, out, copy, nrm, dr);
   return launch_status(what);
@@ -494,12 +363,13 @@ static int launch_fwd(const RowsLd& E, const float* x, int64_t M, const float* W
 template <int DI, int DO, bool DROP>
 static int launch_bwd(const RowsLd& G, const RowsLd& En, const float* nrm, int64_t M,
                       const float* W1, const float* W2, const RowsLd& El, const float* x,
-                      const RowsLd& add, float* gz, float* dE, float* gx, const NgDrop& dr,
+                      const RowsLd& add, float* gz, float* dE, float* gx, const DropSite& dr,
                       hipStream_t st, const char* what) {
   constexpr size_t lds = (size_t)2 * DI * (DO + 4) * sizeof(float);
-  static int cache[kNgMaxDev] = {};
+  static int cache[kMaxDev] = {};
   int per_cu = 1;
-  if (ng_prepare(ngcf_bwd_kernel<DI, DO, DROP>, lds, cache, &per_cu, what)) return -1;
+  if (prepare_launch(ngcf_bwd_kernel<DI, DO, DROP>, kNgThreads, lds, cache, &per_cu, what))
+    return -1;
   hipLaunchKernelGGL((ngcf_bwd_kernel<DI, DO, DROP>), dim3(ng_grid(M, per_cu)), dim3(kNgThreads), lds, st,
                      G, En, nrm, M, W1, W2, El, x, add, gz, dE, gx, dr);
   return launch_status(what);
@@ -547,7 +417,7 @@ extern "C" int mirec_ngcf_layer_fwd_f32(const mirec_rows_ld* E, const float* x, 
               what);
     return -1;
   }
-  NgDrop dr;
+  DropSite dr;
   if (ng_drop(p, seed, counter, drawn, &dr, what)) return -1;
   if (n == 0) return 0;
   const RowsLd e = ng_rows(E), o = ng_rows(out);
@@ -579,7 +449,7 @@ extern "C" int mirec_ngcf_layer_bwd_f32(const mirec_rows_ld* G, const mirec_rows
               what);
     return -1;
   }
-  NgDrop dr;
+  DropSite dr;
   if (ng_drop(p, seed, counter, drawn, &dr, what)) return -1;
   if (n == 0) return 0;
   const RowsLd g = ng_rows(G), en = ng_rows(E_next), el = ng_rows(E),

@@ -19,6 +19,7 @@
 // The sampler only depends on the data pipeline (never on model state), so the
 // trainer runs it ahead of the model step on a side stream.
 #include "common.h"
+#include "drop.h"
 
 namespace mirec {
 
@@ -739,17 +740,10 @@ __global__ __launch_bounds__(256) void used_bitmap_kernel(const int64_t* __restr
 
 // ---- alias-table fast mode (labelled non-parity; include/mirec.h mirec_sample_alias)
 // Each draw is independent: one lane per (batch, j, k) slot, counter-based
-// random bits (splitmix64 of seed and draw id), Walker/Vose column + threshold,
+// random bits (drop.h's mix64 of seed and draw id), Walker/Vose column + threshold,
 // rejection by redrawing with the next attempt number. No serial walk, so a
 // whole chunk of batches is one wide launch.
 constexpr int kAliasTries = 4096;
-
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
 
 __device__ __forceinline__ int32_t alias_draw(const uint32_t* __restrict__ thr,
                                               const int32_t* __restrict__ alias, uint64_t n_cols,

@@ -5,6 +5,7 @@
 // this entry point runs a sampled subset fast enough for the -m gpu test suite.
 #include "common.h"
 #include "adam_math.h"
+#include "drop.h"
 
 #pragma clang fp contract(off)
 
@@ -37,13 +38,6 @@ __global__ __launch_bounds__(256) void selftest_sqrt(uint64_t stride,
   atomicAdd(&out[1], tested);
 }
 
-__device__ __forceinline__ uint64_t st_mix(uint64_t z) {
-  z += 0x9e3779b97f4a7c15ull;
-  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-  z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-  return z ^ (z >> 31);
-}
-
 __device__ __forceinline__ float st_make(uint64_t r, int elo, int ehi, int edge) {
   const int e = elo + (int)((r >> 32) % (uint64_t)(ehi - elo));
   uint32_t mant = (uint32_t)r & 0x7fffffu;
@@ -60,7 +54,7 @@ __global__ __launch_bounds__(256) void selftest_div(uint64_t seed, uint64_t n,
   unsigned long long bad = 0, tested = 0;
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += (uint64_t)gridDim.x * blockDim.x) {
-    const uint64_t r1 = st_mix(seed ^ (2 * i)), r2 = st_mix(seed ^ (2 * i + 1));
+    const uint64_t r1 = mix64(seed ^ (2 * i)), r2 = mix64(seed ^ (2 * i + 1));
     const int edge = (int)(r2 & 15);
     float a = st_make(r1, -60, 40, edge == 4 ? 1 : edge == 5 ? 2 : edge == 6 ? 3 : 0);
     const float b = st_make(r2, -40, 40, edge == 7 ? 1 : edge == 8 ? 2 : edge == 9 ? 3 : 0);

@@ -19,6 +19,7 @@
 //
 // Layout: D/4 lanes per row (float4 per lane), 64/(D/4) rows per wave for K9a.
 #include "common.h"
+#include "drop.h"
 
 namespace mirec {
 
@@ -33,37 +34,8 @@ __device__ __forceinline__ float sum4(float4 a) { return (a.x + a.y) + (a.z + a.
 
 constexpr int kLnRowsPerBlock = 64;   // K9a backward partial-sum chunk (fixed)
 
-// Dropout folded into K9a / K9d (counter-based draws; the K9d header below spells them out)
-struct LnDrop {
-  uint32_t thr;
-  float scale;
-  uint64_t seed;
-  int64_t* counter;     // forward: read; backward: set to drawn + 1
-  int64_t* drawn;       // forward writes the counter value used; backward reads it
-};
-
-__device__ __forceinline__ uint64_t ln_mix(uint64_t z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-// the key of one draw: the seed and the counter enter separately (seed + c would give
-// site s at step t + 1 the key of site s + 1 at step t: sites' seeds differ by small words)
-__device__ __forceinline__ uint64_t ln_key(uint64_t seed, int64_t c) {
-  return ln_mix(ln_mix(seed) ^ (uint64_t)c);
-}
-
-// keep flags of the four elements e0 .. e0 + 3 (e0 a multiple of 4)
-__device__ __forceinline__ void ln_keep4(uint64_t key, uint64_t e0, uint32_t thr, bool (&k)[4]) {
-  const uint64_t h0 = ln_mix(key ^ (e0 >> 1)), h1 = ln_mix(key ^ ((e0 >> 1) + 1));
-  k[0] = (uint32_t)h0 < thr;
-  k[1] = (uint32_t)(h0 >> 32) < thr;
-  k[2] = (uint32_t)h1 < thr;
-  k[3] = (uint32_t)(h1 >> 32) < thr;
-}
-
+// Dropout is folded into K9a / K9d: the shared counter-based draw (drop.h), element
+// e = row * D + column.
 
 // DROP: SASRec's embedding dropout (sasrec.py:107-114, after the LayerNorm) folded in: the
 // output is drop(LayerNorm(...)), the backward masks the incoming gradient the same way.
@@ -72,7 +44,7 @@ __global__ __launch_bounds__(256) void seq_embed_ln_fwd_kernel(
     const float* __restrict__ E, int64_t n_items, const float* __restrict__ P,
     const int64_t* __restrict__ seq, int64_t n_rows, int L, const float* __restrict__ gamma,
     const float* __restrict__ beta, float eps, float* __restrict__ out,
-    float* __restrict__ mean_out, float* __restrict__ rstd_out, LnDrop dr) {
+    float* __restrict__ mean_out, float* __restrict__ rstd_out, DropSite dr) {
   constexpr int LPR = D / 4, GPW = 64 / LPR;
   const int lane = threadIdx.x & 63;
   const int g = lane / LPR, l = lane % LPR;
@@ -81,7 +53,7 @@ __global__ __launch_bounds__(256) void seq_embed_ln_fwd_kernel(
   uint64_t key = 0;
   if (DROP) {
     const int64_t cv = dr.counter[0];
-    key = ln_key(dr.seed, cv);
+    key = drop_key(dr.seed, cv);
     if (blockIdx.x == 0 && threadIdx.x == 0) dr.drawn[0] = cv;
   }
   if (r >= n_rows) return;
@@ -105,7 +77,7 @@ __global__ __launch_bounds__(256) void seq_embed_ln_fwd_kernel(
   y.w = c.w * rstd * gm.w + bt.w;
   if (DROP) {
     bool k[4];
-    ln_keep4(key, (uint64_t)r * D + 4 * l, dr.thr, k);
+    drop_keep4(key, (uint64_t)r * D + 4 * l, dr.thr, k);
     y.x = k[0] ? y.x * dr.scale : 0.f;
     y.y = k[1] ? y.y * dr.scale : 0.f;
     y.z = k[2] ? y.z * dr.scale : 0.f;
@@ -126,10 +98,10 @@ __global__ __launch_bounds__(256) void seq_embed_ln_bwd_kernel(
     const int64_t* __restrict__ seq, int64_t n_rows, int L, const float* __restrict__ gamma,
     const float* __restrict__ mean_in, const float* __restrict__ rstd_in,
     const float* __restrict__ gy, float* __restrict__ dx, float* __restrict__ ditem,
-    float* __restrict__ part_gamma, float* __restrict__ part_beta, LnDrop dr) {
+    float* __restrict__ part_gamma, float* __restrict__ part_beta, DropSite dr) {
   constexpr int LPR = D / 4, GPW = 64 / LPR;
   const int64_t cv = DROP ? dr.drawn[0] : 0;
-  const uint64_t key = DROP ? ln_key(dr.seed, cv) : 0ull;
+  const uint64_t key = DROP ? drop_key(dr.seed, cv) : 0ull;
   if (DROP && blockIdx.x == 0 && threadIdx.x == 0) dr.counter[0] = cv + 1;   // the next draw
   __shared__ float4 red_g[4 * GPW][LPR];
   __shared__ float4 red_b[4 * GPW][LPR];
@@ -157,7 +129,7 @@ __global__ __launch_bounds__(256) void seq_embed_ln_bwd_kernel(
     float4 gv = reinterpret_cast<const float4*>(gy + r * D)[l];
     if (DROP) {
       bool k[4];
-      ln_keep4(key, (uint64_t)r * D + 4 * l, dr.thr, k);
+      drop_keep4(key, (uint64_t)r * D + 4 * l, dr.thr, k);
       gv.x = k[0] ? gv.x * dr.scale : 0.f;
       gv.y = k[1] ? gv.y * dr.scale : 0.f;
       gv.z = k[2] ? gv.z * dr.scale : 0.f;
@@ -204,20 +176,16 @@ __global__ __launch_bounds__(256) void seq_embed_ln_bwd_kernel(
 //   FeedForward: LayerNorm(dropout(hidden) + input_tensor), reference layers.py:338-552):
 //   y = LayerNorm(drop(a) + b) in one pass (the sum is never written), and its backward
 //   from the saved mean / rstd with x = drop(a) + b recomputed; same arithmetic as K9a.
-//   DROP: the hidden dropout folded in (torch ran it as its own kernel each way). Draws are
-//   counter-based: key = splitmix64(splitmix64(seed) ^ c) (ln_key; numpy restatement in
-//   tests/drop_spec.py), c the device counter's value at the forward (saved in drawn[0]);
-//   the backward redraws from drawn[0] and sets the counter to c + 1
-//   (one store: a last-block ticket over the forward's 12,800 workgroups serialised that
-//   many atomics on one word, 153 us against 28 for the kernel itself);
-//   element e = row * D + column is kept iff the 32-bit half e & 1 of
-//   splitmix64(key ^ (e >> 1)) is below thr; a kept element is scaled by 1 / (1 - p).
+//   DROP: the hidden dropout folded in (torch ran it as its own kernel each way), drawn by
+//   drop.h's rule. The backward sets the counter with one store: a last-block ticket over
+//   the forward's 12,800 workgroups serialised that many atomics on one word, 153 us against
+//   28 for the kernel itself.
 template <int D, bool DROP>
 __global__ __launch_bounds__(256) void add_ln_fwd_kernel(
     const float* __restrict__ A, const float* __restrict__ Bv, int64_t n_rows,
     const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
     float* __restrict__ out, float* __restrict__ mean_out, float* __restrict__ rstd_out,
-    LnDrop dr) {
+    DropSite dr) {
   constexpr int LPR = D / 4, GPW = 64 / LPR;
   const int lane = threadIdx.x & 63;
   const int g = lane / LPR, l = lane % LPR;
@@ -226,14 +194,14 @@ __global__ __launch_bounds__(256) void add_ln_fwd_kernel(
   uint64_t key = 0;
   if (DROP) {
     const int64_t c = dr.counter[0];
-    key = ln_key(dr.seed, c);
+    key = drop_key(dr.seed, c);
     if (blockIdx.x == 0 && threadIdx.x == 0) dr.drawn[0] = c;
   }
   if (r < n_rows) {
     float4 a = reinterpret_cast<const float4*>(A + r * D)[l];
     if (DROP) {
       bool k[4];
-      ln_keep4(key, (uint64_t)r * D + 4 * l, dr.thr, k);
+      drop_keep4(key, (uint64_t)r * D + 4 * l, dr.thr, k);
       a.x = k[0] ? a.x * dr.scale : 0.f;
       a.y = k[1] ? a.y * dr.scale : 0.f;
       a.z = k[2] ? a.z * dr.scale : 0.f;
@@ -269,7 +237,7 @@ __global__ __launch_bounds__(256) void add_ln_bwd_kernel(
     const float* __restrict__ gamma, const float* __restrict__ mean_in,
     const float* __restrict__ rstd_in, const float* __restrict__ gy, float* __restrict__ dxb,
     float* __restrict__ dxa, float* __restrict__ part_gamma, float* __restrict__ part_beta,
-    LnDrop dr) {
+    DropSite dr) {
   constexpr int LPR = D / 4, GPW = 64 / LPR;
   __shared__ float4 red_g[4 * GPW][LPR];
   __shared__ float4 red_b[4 * GPW][LPR];
@@ -278,7 +246,7 @@ __global__ __launch_bounds__(256) void add_ln_bwd_kernel(
   const int g = lane / LPR, l = lane % LPR;
   const float4 gm = reinterpret_cast<const float4*>(gamma)[l];
   const int64_t c = DROP ? dr.drawn[0] : 0;
-  const uint64_t key = DROP ? ln_key(dr.seed, c) : 0ull;
+  const uint64_t key = DROP ? drop_key(dr.seed, c) : 0ull;
   if (DROP && blockIdx.x == 0 && threadIdx.x == 0) dr.counter[0] = c + 1;   // the next draw
   float4 ag = make_float4(0.f, 0.f, 0.f, 0.f), ab = ag;
   const int64_t base = (int64_t)blockIdx.x * kLnRowsPerBlock;
@@ -288,7 +256,7 @@ __global__ __launch_bounds__(256) void add_ln_bwd_kernel(
     float4 a = reinterpret_cast<const float4*>(A + r * D)[l];
     bool k[4] = {true, true, true, true};
     if (DROP) {
-      ln_keep4(key, (uint64_t)r * D + 4 * l, dr.thr, k);
+      drop_keep4(key, (uint64_t)r * D + 4 * l, dr.thr, k);
       a.x = k[0] ? a.x * dr.scale : 0.f;
       a.y = k[1] ? a.y * dr.scale : 0.f;
       a.z = k[2] ? a.z * dr.scale : 0.f;
@@ -529,7 +497,7 @@ static int seq_embed_ln_fwd_impl(const float* item_table, int64_t n_items,
                                  const float* pos_table, const int64_t* item_seq, int64_t B,
                                  int32_t L, int32_t d, const float* gamma, const float* beta,
                                  float eps, float* out, float* mean, float* rstd,
-                                 const LnDrop* dr, void* stream, const char* what) {
+                                 const DropSite* dr, void* stream, const char* what) {
   const int64_t n = B * L;
   if (n == 0) return 0;
   if (!item_table || !pos_table || !item_seq || !gamma || !beta || !out || !mean || !rstd ||
@@ -538,7 +506,7 @@ static int seq_embed_ln_fwd_impl(const float* item_table, int64_t n_items,
     return -1;
   }
   hipStream_t st = (hipStream_t)stream;
-  LnDrop none;
+  DropSite none;
   memset(&none, 0, sizeof(none));
 #define MIREC_LNF(DD)                                                                        \
   case DD: {                                                                                 \
@@ -576,7 +544,7 @@ static int seq_embed_ln_bwd_impl(const float* item_table, int64_t n_items,
                                  int32_t L, int32_t d, const float* gamma, const float* mean,
                                  const float* rstd, const float* grad_out, float* dx,
                                  float* ditem, float* part_gamma, float* part_beta,
-                                 const LnDrop* dr, void* stream, const char* what) {
+                                 const DropSite* dr, void* stream, const char* what) {
   const int64_t n = B * L;
   if (n == 0) return 0;
   if (!item_table || !pos_table || !item_seq || !gamma || !mean || !rstd || !grad_out ||
@@ -586,7 +554,7 @@ static int seq_embed_ln_bwd_impl(const float* item_table, int64_t n_items,
   }
   hipStream_t st = (hipStream_t)stream;
   const dim3 grd((unsigned)mirec_seq_embed_ln_partials(n));
-  LnDrop none;
+  DropSite none;
   memset(&none, 0, sizeof(none));
 #define MIREC_LNB(DD)                                                                        \
   case DD:                                                                                   \
@@ -614,7 +582,7 @@ static int seq_embed_ln_bwd_impl(const float* item_table, int64_t n_items,
 
 static int add_ln_fwd_impl(const float* a, const float* b, int64_t n, int32_t d,
                            const float* gamma, const float* beta, float eps, float* out,
-                           float* mean, float* rstd, const LnDrop* dr, void* stream,
+                           float* mean, float* rstd, const DropSite* dr, void* stream,
                            const char* what) {
   if (n == 0) return 0;
   if (!a || !b || !gamma || !beta || !out || !mean || !rstd || n < 0) {
@@ -622,7 +590,7 @@ static int add_ln_fwd_impl(const float* a, const float* b, int64_t n, int32_t d,
     return -1;
   }
   hipStream_t st = (hipStream_t)stream;
-  LnDrop none;
+  DropSite none;
   memset(&none, 0, sizeof(none));
 #define MIREC_ALF(DD)                                                                        \
   case DD: {                                                                                 \
@@ -652,7 +620,7 @@ static int add_ln_fwd_impl(const float* a, const float* b, int64_t n, int32_t d,
 static int add_ln_bwd_impl(const float* a, const float* b, int64_t n, int32_t d,
                            const float* gamma, const float* mean, const float* rstd,
                            const float* grad_out, float* dxb, float* dxa, float* part_gamma,
-                           float* part_beta, const LnDrop* dr, void* stream, const char* what) {
+                           float* part_beta, const DropSite* dr, void* stream, const char* what) {
   if (n == 0) return 0;
   if (!a || !b || !gamma || !mean || !rstd || !grad_out || !dxb || !part_gamma || !part_beta ||
       n < 0 || (dr && !dxa)) {
@@ -661,7 +629,7 @@ static int add_ln_bwd_impl(const float* a, const float* b, int64_t n, int32_t d,
   }
   hipStream_t st = (hipStream_t)stream;
   const dim3 grd((unsigned)mirec_seq_embed_ln_partials(n));
-  LnDrop none;
+  DropSite none;
   memset(&none, 0, sizeof(none));
 #define MIREC_ALB(DD)                                                                        \
   case DD:                                                                                   \
@@ -684,20 +652,6 @@ static int add_ln_bwd_impl(const float* a, const float* b, int64_t n, int32_t d,
   }
 #undef MIREC_ALB
   return launch_status(what);
-}
-
-static int ln_drop_args(float p, uint64_t seed, int64_t* counter, int64_t* drawn, LnDrop* dr,
-                        const char* what) {
-  if (!(p > 0.f && p < 1.f) || !drawn || !counter) {
-    set_error("%s: dropout %g needs 0 < p < 1, the counter and the drawn word", what, (double)p);
-    return -1;
-  }
-  dr->thr = (uint32_t)fmin(4294967295.0, ldexp(1.0 - (double)p, 32));
-  dr->scale = 1.0f / (1.0f - p);
-  dr->seed = seed;
-  dr->counter = counter;
-  dr->drawn = drawn;
-  return 0;
 }
 
 extern "C" int mirec_add_ln_fwd_f32(const float* a, const float* b, int64_t n, int32_t d,
@@ -743,8 +697,8 @@ extern "C" int mirec_seq_embed_ln_drop_fwd_f32(const float* item_table, int64_t 
                                                float p, uint64_t seed, int64_t* counter,
                                                int64_t* drawn, float* out, float* mean,
                                                float* rstd, void* stream) {
-  LnDrop dr;
-  if (ln_drop_args(p, seed, counter, drawn, &dr, "mirec_seq_embed_ln_drop_fwd_f32")) return -1;
+  DropSite dr;
+  if (drop_site(p, seed, counter, drawn, &dr, "mirec_seq_embed_ln_drop_fwd_f32")) return -1;
   return seq_embed_ln_fwd_impl(item_table, n_items, pos_table, item_seq, B, L, d, gamma, beta,
                                eps, out, mean, rstd, &dr, stream,
                                "mirec_seq_embed_ln_drop_fwd_f32");
@@ -759,8 +713,8 @@ extern "C" int mirec_seq_embed_ln_drop_bwd_f32(const float* item_table, int64_t 
                                                int64_t* counter, float* dx, float* ditem,
                                                float* part_gamma, float* part_beta,
                                                void* stream) {
-  LnDrop dr;
-  if (ln_drop_args(p, seed, counter, drawn, &dr, "mirec_seq_embed_ln_drop_bwd_f32")) return -1;
+  DropSite dr;
+  if (drop_site(p, seed, counter, drawn, &dr, "mirec_seq_embed_ln_drop_bwd_f32")) return -1;
   return seq_embed_ln_bwd_impl(item_table, n_items, pos_table, item_seq, B, L, d, gamma, mean,
                                rstd, grad_out, dx, ditem, part_gamma, part_beta, &dr, stream,
                                "mirec_seq_embed_ln_drop_bwd_f32");
@@ -771,8 +725,8 @@ extern "C" int mirec_add_ln_drop_fwd_f32(const float* a, const float* b, int64_t
                                          float p, uint64_t seed, int64_t* counter,
                                          int64_t* drawn, float* out, float* mean, float* rstd,
                                          void* stream) {
-  LnDrop dr;
-  if (ln_drop_args(p, seed, counter, drawn, &dr, "mirec_add_ln_drop_fwd_f32")) return -1;
+  DropSite dr;
+  if (drop_site(p, seed, counter, drawn, &dr, "mirec_add_ln_drop_fwd_f32")) return -1;
   return add_ln_fwd_impl(a, b, n, d, gamma, beta, eps, out, mean, rstd, &dr, stream,
                          "mirec_add_ln_drop_fwd_f32");
 }
@@ -783,8 +737,8 @@ extern "C" int mirec_add_ln_drop_bwd_f32(const float* a, const float* b, int64_t
                                          uint64_t seed, int64_t* drawn, int64_t* counter,
                                          float* dx_a, float* dx_b, float* part_gamma,
                                          float* part_beta, void* stream) {
-  LnDrop dr;
-  if (ln_drop_args(p, seed, counter, drawn, &dr, "mirec_add_ln_drop_bwd_f32")) return -1;
+  DropSite dr;
+  if (drop_site(p, seed, counter, drawn, &dr, "mirec_add_ln_drop_bwd_f32")) return -1;
   return add_ln_bwd_impl(a, b, n, d, gamma, mean, rstd, grad_out, dx_b, dx_a, part_gamma,
                          part_beta, &dr, stream, "mirec_add_ln_drop_bwd_f32");
 }

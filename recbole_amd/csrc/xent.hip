@@ -54,10 +54,10 @@
 //   K12b     116 / 17408   163 / 33792   238 / 33280   398 / 66048
 //   K12c     127 / 18944   183 / 35328   232 / 34048   386 / 66816
 #include "common.h"
+#include "mfma.h"
 
 namespace mirec {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 constexpr int kXeThreads = 256;
 constexpr int kXeFwd = 0, kXeQuery = 1, kXeItem = 2;
@@ -179,8 +179,8 @@ __global__ __launch_bounds__(kXeThreads, D <= 128 ? 2 : 1) void xent_kernel(
 #pragma unroll
       for (int s2 = 0; s2 < D / 4; ++s2) {
         const float2 a = *reinterpret_cast<const float2*>(arow + 4 * s2);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, ub[2 * s2], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, ub[2 * s2 + 1], acc, 0, 0, 0);
+        acc = mfma_32x32x2(a.x, ub[2 * s2], acc);
+        acc = mfma_32x32x2(a.y, ub[2 * s2 + 1], acc);
       }
       const int64_t sb = base + 32 * sub;
       if constexpr (MODE == kXeFwd) {
@@ -221,8 +221,7 @@ __global__ __launch_bounds__(kXeThreads, D <= 128 ? 2 : 1) void xent_kernel(
               tile[cur] + (32 * sub + (r & 3) + 8 * (r >> 2) + 4 * h) * LDR + j;
 #pragma unroll
           for (int cb = 0; cb < NCB; ++cb)
-            oacc[cb] = __builtin_amdgcn_mfma_f32_32x32x2f32(acc[r], brow[32 * cb], oacc[cb],
-                                                            0, 0, 0);
+            oacc[cb] = mfma_32x32x2(acc[r], brow[32 * cb], oacc[cb]);
         }
       }
     }
