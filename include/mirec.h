@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define MIREC_ABI_VERSION 23
+#define MIREC_ABI_VERSION 24
 
 int mirec_abi_version(void);
 const char* mirec_last_error(void);
@@ -765,6 +765,60 @@ int mirec_full_ce_bwd_f32(const float* S, int64_t B, const float* E, int64_t I, 
                           const int64_t* target, const float* lse, const float* g_dev,
                           int32_t splits, float* gS, float* dE, void* workspace,
                           void* stream);
+/* K12 over gathered rows (K17, BERT4Rec's loss over masked positions, bert4rec.py:203-233:
+ * replaces the [B*M, L] multi-hot bmm gather, the [B, M, n_items] logits, the 'none'-reduced
+ * cross entropy times targets and their backward).
+ * X[n_x, d]: the matrix the queries live in; query r is X[row[r]], loaded straight into the
+ *   MFMA operand (no gathered copy); target[R]; n_rows_dev: an int32 DEVICE count, nullable.
+ *   Only queries r < min(R, *n_rows_dev) exist: a 128-query workgroup at or past the count
+ *   exits at once and K12c's query sweep ends there. row[r] of an existing query must lie
+ *   in [0, n_x); later entries are never read.
+ * For r past the count lse[r] = loss_rows[r] = 0 and gS[r] = 0 exactly. gS is compact
+ *   [R, d]; dE is [I, d], every row written.
+ * The backward's factor is g_dev[0] AS IT STANDS (no division by R): the caller folds
+ *   1 / count in on the device.
+ * Splits, workspace (the K12 sizes for B = R) and every summation order are K12's: with
+ *   row = 0 .. R-1 and n_rows_dev null the forward outputs are K12's bit for bit, and the
+ *   backward's are K12's for g_dev[0] = R (where K12's factor R / R is exactly 1). */
+int mirec_rows_ce_fwd_f32(const float* X, int64_t n_x, const int64_t* row, int64_t R,
+                               const int32_t* n_rows_dev, const float* E, int64_t I, int32_t d,
+                               const int64_t* target, int32_t splits, float* lse,
+                               float* loss_rows, void* workspace, void* stream);
+int mirec_rows_ce_bwd_f32(const float* X, int64_t n_x, const int64_t* row, int64_t R,
+                               const int32_t* n_rows_dev, const float* E, int64_t I, int32_t d,
+                               const int64_t* target, const float* lse, const float* g_dev,
+                               int32_t splits, float* gS, float* dE, void* workspace,
+                               void* stream);
+
+/* ---------------------------------------------------------------------------
+ * K17  BERT4Rec's Cloze task on the device (csrc/cloze.hip; tests/cloze_spec.py).
+ * mirec_cloze_mask (K17a) replaces BERT4Rec.reconstruct_train_data (bert4rec.py:111-156:
+ *   the batch copied to the host and a Python loop over every position). item_seq [B, L]
+ *   int64, L <= 64; M = int(mask_ratio * L) slots per row, 1 <= M <= L; n_items - 1 > L.
+ *   Element e = b*L + t with item > 0 is masked iff !drop_keep(drop_key(seed, *counter), e,
+ *   drop_threshold(mask_ratio)) (csrc/drop.h); the counter is only read — the caller
+ *   advances it by one after the launch. masked_seq [B, L] (masked positions = n_items, the
+ *   mask token), pos_items / masked_index / neg_items [B, M] left padded with 0, the LAST M
+ *   of a row with more (_padding_sequence). neg_items null: not drawn; else each kept slot
+ *   gets an id in [1, n_items - 1] not among its row's L original entries (rule: cloze.hip).
+ * mirec_cloze_compact (K17b) replaces targets = (masked_index > 0) (bert4rec.py:229) as a
+ *   dense row list, one launch: the [B, M] slots with masked_index > 0 in ascending
+ *   (b, slot) order -> act_row [B*M] int64 = b*L + index, act_target [B*M] int64,
+ *   n_act int32 (device), slot_of [B*L] int32 = compact row of that position or -1.
+ *   Entries past n_act are 0. B*L and B*M must fit int32.
+ * mirec_rows_from_slots_f32 (K17c) replaces the backward of the multi-hot bmm
+ *   (bert4rec.py:208-213): gX[p] = gS[slot_of[p]] or zeros, gX [n_pos, d] written once.
+ * No atomics, no host synchronisation.
+ * ------------------------------------------------------------------------- */
+int mirec_cloze_mask(const int64_t* item_seq, int64_t B, int32_t L, int32_t M, int64_t n_items,
+                     double mask_ratio, uint64_t seed, const int64_t* counter,
+                     int64_t* masked_seq, int64_t* pos_items, int64_t* masked_index,
+                     int64_t* neg_items, void* stream);
+int mirec_cloze_compact(const int64_t* masked_index, const int64_t* pos_items, int64_t B,
+                        int32_t L, int32_t M, int64_t* act_row, int64_t* act_target,
+                        int32_t* n_act, int32_t* slot_of, void* stream);
+int mirec_rows_from_slots_f32(const float* gS, const int32_t* slot_of, int64_t n_pos, int32_t d,
+                              float* gX, void* stream);
 
 /* ---------------------------------------------------------------------------
  * K7  Graph propagation (LightGCN): CSR SpMM with a fused epilogue.
@@ -1056,6 +1110,11 @@ int mirec_attn_bwd_f32(const float* q, const float* k, const float* v, const flo
  * where attention is allowed). item_seq: [B, L] int64. */
 int mirec_seq_attn_mask_f32(const int64_t* item_seq, int64_t B, int32_t L, float* mask,
                             void* stream);
+/* BERT4Rec.get_attention_mask (bert4rec.py:90-97), the bidirectional mask, in one launch and
+ * in the [B, 1, L, L] layout K9e takes: (1 - [item_seq[b][j] > 0]) * -10000 for every query
+ * index i — the reference's [B, 1, 1, L] values broadcast, -0.0 where attention is allowed. */
+int mirec_seq_attn_mask_bidir_f32(const int64_t* item_seq, int64_t B, int32_t L, float* mask,
+                                  void* stream);
 /* GELU (erf form) of the feed-forward block, forward and backward, elementwise. */
 int mirec_gelu_fwd_f32(const float* x, int64_t n, float* y, void* stream);
 int mirec_gelu_bwd_f32(const float* x, const float* g, int64_t n, float* dx, void* stream);

@@ -178,6 +178,7 @@ SIGNATURES = {
     "mirec_attn_bwd_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32,
                                    c_float, _P, _P, _P, _P]),
     "mirec_seq_attn_mask_f32": (c_int, [_P, c_int64, c_int32, _P, _P]),
+    "mirec_seq_attn_mask_bidir_f32": (c_int, [_P, c_int64, c_int32, _P, _P]),
     "mirec_gelu_fwd_f32": (c_int, [_P, c_int64, _P, _P]),
     "mirec_gelu_bwd_f32": (c_int, [_P, _P, c_int64, _P, _P]),
     "mirec_add_ln_fwd_f32": (c_int, [_P, _P, c_int64, c_int32, _P, _P, c_float, _P, _P, _P, _P]),
@@ -257,6 +258,14 @@ SIGNATURES = {
                                       _P]),
     "mirec_full_ce_bwd_f32": (c_int, [_P, c_int64, _P, c_int64, c_int32, _P, _P, _P, c_int32, _P,
                                       _P, _P, _P]),
+    "mirec_rows_ce_fwd_f32": (c_int, [_P, c_int64, _P, c_int64, _P, _P, c_int64, c_int32, _P,
+                                      c_int32, _P, _P, _P, _P]),
+    "mirec_rows_ce_bwd_f32": (c_int, [_P, c_int64, _P, c_int64, _P, _P, c_int64, c_int32, _P,
+                                      _P, _P, c_int32, _P, _P, _P, _P]),
+    "mirec_cloze_mask": (c_int, [_P, c_int64, c_int32, c_int32, c_int64, c_double,
+                                 ctypes.c_uint64, _P, _P, _P, _P, _P, _P]),
+    "mirec_cloze_compact": (c_int, [_P, _P, c_int64, c_int32, c_int32, _P, _P, _P, _P, _P]),
+    "mirec_rows_from_slots_f32": (c_int, [_P, _P, c_int64, c_int32, _P, _P]),
     "mirec_spmm_csr_f32": (c_int, [_P, _P, _P, c_int64, c_int32, _P, _P, _P, c_int64, c_int32,
                                    _P, _P, c_int64, _P, ctypes.POINTER(RowsRef),
                                    ctypes.POINTER(SpmmEpilogue), _P]),
@@ -344,7 +353,7 @@ SIGNATURES = {
                                      _P, _P]),
 }
 
-ABI_VERSION = 23
+ABI_VERSION = 24
 
 
 class NativeError(RuntimeError):

@@ -1,6 +1,6 @@
 """Default configuration values, restated as Python data from the reference's
 property files (recbole/properties/overall.yaml, dataset/sample.yaml,
-dataset/ml-100k.yaml, model/{BPR,LightGCN,NGCF,SASRec,GRU4Rec,DeepFM,NeuMF,MultiDAE,MultiVAE}.yaml,
+dataset/ml-100k.yaml, model/{BPR,LightGCN,NGCF,SASRec,GRU4Rec,BERT4Rec,DeepFM,NeuMF,MultiDAE,MultiVAE}.yaml,
 quick_start_config/{sequential,context-aware}.yaml)."""
 from recbole_amd.utils.enum_type import ModelType
 
@@ -63,6 +63,11 @@ MODEL_DEFAULTS = {
                    layer_norm_eps=1e-12, initializer_range=0.02, loss_type='CE'),
     'GRU4Rec': dict(embedding_size=64, hidden_size=128, num_layers=1, dropout_prob=0.3,
                     loss_type='CE'),
+    # ce_kernel: the build's key ('library' = the reference's op sequence, 'fused' = K17 + K12)
+    'BERT4Rec': dict(n_layers=2, n_heads=2, hidden_size=64, inner_size=256,
+                     hidden_dropout_prob=0.5, attn_dropout_prob=0.5, hidden_act='gelu',
+                     layer_norm_eps=1e-12, initializer_range=0.02, mask_ratio=0.2,
+                     loss_type='CE', ce_kernel='library'),
     'DeepFM': dict(embedding_size=10, mlp_hidden_size=[128, 128, 128], dropout_prob=0.2),
     'NeuMF': dict(mf_embedding_size=64, mlp_embedding_size=64, mlp_hidden_size=[128, 64, 32],
                   dropout_prob=0.0, weight_decay=1e-08, mf_train=True, mlp_train=True,

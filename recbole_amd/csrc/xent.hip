@@ -53,6 +53,10 @@
 //   K12a     103 / 17408   107 / 33792   191 / 66560   282 / 66048
 //   K12b     116 / 17408   163 / 33792   238 / 33280   398 / 66048
 //   K12c     127 / 18944   183 / 35328   232 / 34048   386 / 66816
+// Over gathered rows (ROWS, K17: mirec_rows_ce_*), the same LDS, no spills:
+//   K12a     103           107           191           282
+//   K12b     115           162           236           411
+//   K12c     126           182           231           384
 #include "common.h"
 #include "mfma.h"
 
@@ -75,12 +79,20 @@ template <int D, int MODE> struct XeSub {
 //   kXeFwd:   pm / ps / pt [gridDim.y, B] partial (max, sum, target logit or -inf)
 //   kXeQuery: out [gridDim.y, B, D] partial gS (gS itself when gridDim.y == 1)
 //   kXeItem:  out = dE [I, D]
-template <int D, int MODE>
+// ROWS (K17, the queries are gathered rows of a larger matrix): query r is row rows[r] of the
+// query matrix, loaded straight into the operand (K12a/b) or the staged tile (K12c); only
+// queries r < min(count given to the launch, *n_dev) exist (n_dev null: all of them). A
+// query workgroup that starts at or past that count leaves at once (K12b without a split
+// writes its rows' zeros first), K12c's sweep ends there, and the backward's factor is
+// g_dev[0] as it stands. Everything else — tiles, k order, summation orders — is the code
+// below, shared.
+template <int D, int MODE, bool ROWS>
 __global__ __launch_bounds__(kXeThreads, D <= 128 ? 2 : 1) void xent_kernel(
     const float* __restrict__ X, int64_t NX, const float* __restrict__ Y, int64_t NY,
     const int64_t* __restrict__ target, const float* __restrict__ lse,
     const float* __restrict__ g_dev, int64_t B, int64_t span, float* __restrict__ out,
-    float* __restrict__ pm, float* __restrict__ ps, float* __restrict__ pt) {
+    float* __restrict__ pm, float* __restrict__ ps, float* __restrict__ pt,
+    const int64_t* __restrict__ rows, const int32_t* __restrict__ n_dev) {
   constexpr int LDR = D + 2;
   constexpr int V4 = D / 4;
   constexpr int NT = XeSub<D, MODE>::n;
@@ -97,16 +109,36 @@ __global__ __launch_bounds__(kXeThreads, D <= 128 ? 2 : 1) void xent_kernel(
   const int h = lane >> 5;
   const int64_t xb = ((int64_t)blockIdx.x * 4 + w) * 32;
   const int64_t x = xb + j;
-  const bool xv = x < NX;
   const int64_t ylo = (int64_t)blockIdx.y * span;
-  const int64_t yhi = min(NY, ylo + span);
+  int64_t nx = NX, yhi = min(NY, ylo + span);
+  if constexpr (ROWS) {
+    const int64_t cnt = n_dev ? (int64_t)max(n_dev[0], 0) : INT64_MAX;
+    if constexpr (MODE == kXeItem) {
+      yhi = min(yhi, cnt);
+    } else {
+      nx = min(NX, cnt);
+      const int64_t b0 = (int64_t)blockIdx.x * 128;
+      if (b0 >= nx) {                      // no live query in this workgroup
+        if (MODE == kXeQuery && gridDim.y == 1) {
+          const int64_t n4 = (min(NX, b0 + 128) - b0) * (D / 4);
+          float4* z = reinterpret_cast<float4*>(out + b0 * D);
+          for (int64_t e = threadIdx.x; e < n4; e += kXeThreads)
+            z[e] = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        return;
+      }
+    }
+  }
+  const bool xv = x < nx;
+  int64_t xsrc = x;                        // the row of X this lane's fixed row is read from
+  if constexpr (ROWS && MODE != kXeItem) xsrc = xv ? rows[x] : 0;
 
   // lane (j, h) holds fixed row x's elements in the permuted k order
   float ub[D / 2];
 #pragma unroll
   for (int s2 = 0; s2 < D / 4; ++s2) {
     float2 v = make_float2(0.f, 0.f);
-    if (xv) v = *reinterpret_cast<const float2*>(X + x * D + 4 * s2 + 2 * h);
+    if (xv) v = *reinterpret_cast<const float2*>(X + xsrc * D + 4 * s2 + 2 * h);
     ub[2 * s2] = v.x;
     ub[2 * s2 + 1] = v.y;
   }
@@ -115,7 +147,7 @@ __global__ __launch_bounds__(kXeThreads, D <= 128 ? 2 : 1) void xent_kernel(
   float m = -INFINITY, s = 0.f, tl = -INFINITY;               // K12a
   float lq = 0.f, scale = 0.f;
   int64_t tq = -1;
-  if (MODE != kXeFwd) scale = g_dev[0] / (float)B;
+  if (MODE != kXeFwd) scale = ROWS ? g_dev[0] : g_dev[0] / (float)B;
   if (MODE != kXeItem && xv) tq = target[x];
   if (MODE == kXeQuery && xv) lq = lse[x];
   constexpr int NCB = MODE == kXeFwd ? 1 : D / 32;
@@ -136,7 +168,11 @@ __global__ __launch_bounds__(kXeThreads, D <= 128 ? 2 : 1) void xent_kernel(
       const int row = f / V4;
       const int c4 = f - row * V4;
       const int64_t y = base + row;
-      pf[k] = y < yhi ? Y4[y * V4 + c4] : make_float4(0.f, 0.f, 0.f, 0.f);
+      if constexpr (ROWS && MODE == kXeItem) {
+        pf[k] = y < yhi ? Y4[rows[y] * V4 + c4] : make_float4(0.f, 0.f, 0.f, 0.f);
+      } else {
+        pf[k] = y < yhi ? Y4[y * V4 + c4] : make_float4(0.f, 0.f, 0.f, 0.f);
+      }
     }
   };
   auto store_tile = [&](float* dst) {
@@ -253,8 +289,10 @@ __global__ __launch_bounds__(kXeThreads, D <= 128 ? 2 : 1) void xent_kernel(
     for (int r = 0; r < 16; ++r) {
       const int64_t xr = xb + (r & 3) + 8 * (r >> 2) + 4 * h;
       if (xr < NX) {
+        const bool live = !ROWS || MODE == kXeItem || xr < nx;    // a dead query's row: zeros
 #pragma unroll
-        for (int cb = 0; cb < NCB; ++cb) dst[xr * D + 32 * cb + j] = oacc[cb][r];
+        for (int cb = 0; cb < NCB; ++cb)
+          dst[xr * D + 32 * cb + j] = live ? oacc[cb][r] : 0.f;
       }
     }
   }
@@ -263,9 +301,15 @@ __global__ __launch_bounds__(kXeThreads, D <= 128 ? 2 : 1) void xent_kernel(
 // Fold the item splits' partials per query, ascending split order.
 __global__ __launch_bounds__(256) void xent_finish_kernel(
     int64_t B, int S, const float* __restrict__ pm, const float* __restrict__ ps,
-    const float* __restrict__ pt, float* __restrict__ lse, float* __restrict__ loss_rows) {
+    const float* __restrict__ pt, float* __restrict__ lse, float* __restrict__ loss_rows,
+    const int32_t* __restrict__ n_dev) {
   const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (q >= B) return;
+  if (n_dev && q >= (int64_t)n_dev[0]) {      // K17: a query past the count has no partials
+    lse[q] = 0.f;
+    loss_rows[q] = 0.f;
+    return;
+  }
   float m = -INFINITY, s = 0.f, tl = -INFINITY;
   for (int k = 0; k < S; ++k) {
     const int64_t o = (int64_t)k * B + q;
@@ -284,9 +328,14 @@ __global__ __launch_bounds__(256) void xent_finish_kernel(
 // out[e] = sum over the splits of part[k][e], ascending k (n4 float4 elements per split).
 __global__ __launch_bounds__(256) void xent_sum_kernel(int64_t n4, int S,
                                                        const float4* __restrict__ part,
-                                                       float4* __restrict__ out) {
+                                                       float4* __restrict__ out, int d4,
+                                                       const int32_t* __restrict__ n_dev) {
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= n4) return;
+  if (n_dev && e / d4 >= (int64_t)n_dev[0]) {   // K17: the row of a query past the count
+    out[e] = make_float4(0.f, 0.f, 0.f, 0.f);
+    return;
+  }
   float4 a = part[e];
   for (int k = 1; k < S; ++k) {
     const float4 b = part[(int64_t)k * n4 + e];
@@ -338,7 +387,12 @@ extern "C" size_t mirec_full_ce_workspace_size(int64_t B, int64_t I, int32_t d,
 }
 
 #define MIREC_XE_LAUNCH(DD, MODE, grd, ...)                                               \
-  hipLaunchKernelGGL((xent_kernel<DD, MODE>), grd, dim3(kXeThreads), 0, st, __VA_ARGS__)
+  if (rows)                                                                               \
+    hipLaunchKernelGGL((xent_kernel<DD, MODE, true>), grd, dim3(kXeThreads), 0, st,       \
+                       __VA_ARGS__, rows, n_dev);                                         \
+  else                                                                                    \
+    hipLaunchKernelGGL((xent_kernel<DD, MODE, false>), grd, dim3(kXeThreads), 0, st,      \
+                       __VA_ARGS__, (const int64_t*)nullptr, (const int32_t*)nullptr)
 #define MIREC_XE_SWITCH(what, MODE, grd, ...)                                             \
   switch (d) {                                                                            \
     case 32: MIREC_XE_LAUNCH(32, MODE, grd, __VA_ARGS__); break;                          \
@@ -346,17 +400,19 @@ extern "C" size_t mirec_full_ce_workspace_size(int64_t B, int64_t I, int32_t d,
     case 128: MIREC_XE_LAUNCH(128, MODE, grd, __VA_ARGS__); break;                        \
     case 256: MIREC_XE_LAUNCH(256, MODE, grd, __VA_ARGS__); break;                        \
     default:                                                                              \
-      set_error(what ": hidden size %d not in {32,64,128,256}", d);                       \
+      set_error("%s: hidden size %d not in {32,64,128,256}", what, d);                    \
       return -1;                                                                          \
   }
 
-extern "C" int mirec_full_ce_fwd_f32(const float* S, int64_t B, const float* E, int64_t I,
-                                     int32_t d, const int64_t* target, int32_t splits,
-                                     float* lse, float* loss_rows, void* workspace,
-                                     void* stream) {
+// S: the query matrix; B queries — its rows 0 .. B-1 (rows null), or its rows rows[r] of
+// which only the first min(B, *n_dev) exist (K17).
+static int xe_fwd(const float* S, int64_t B, const int64_t* rows, const int32_t* n_dev,
+                  const float* E, int64_t I, int32_t d, const int64_t* target, int32_t splits,
+                  float* lse, float* loss_rows, void* workspace, void* stream,
+                  const char* what) {
   if (B == 0) return 0;
   if (!S || !E || !target || !lse || !loss_rows || !workspace || B < 0 || I <= 0) {
-    set_error("mirec_full_ce_fwd_f32: bad arguments");
+    set_error("%s: bad arguments", what);
     return -1;
   }
   int64_t span;
@@ -366,21 +422,20 @@ extern "C" int mirec_full_ce_fwd_f32(const float* S, int64_t B, const float* E, 
   float* pt = ps + (size_t)ns * B;
   const dim3 grd((unsigned)((B + 127) / 128), (unsigned)ns);
   hipStream_t st = (hipStream_t)stream;
-  MIREC_XE_SWITCH("mirec_full_ce_fwd_f32", kXeFwd, grd, S, B, E, I, target,
-                  (const float*)nullptr, (const float*)nullptr, B, span, (float*)nullptr, pm,
-                  ps, pt)
+  MIREC_XE_SWITCH(what, kXeFwd, grd, S, B, E, I, target, (const float*)nullptr,
+                  (const float*)nullptr, B, span, (float*)nullptr, pm, ps, pt)
   hipLaunchKernelGGL(xent_finish_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, B,
-                     ns, pm, ps, pt, lse, loss_rows);
-  return launch_status("mirec_full_ce_fwd_f32");
+                     ns, pm, ps, pt, lse, loss_rows, rows ? n_dev : (const int32_t*)nullptr);
+  return launch_status(what);
 }
 
-extern "C" int mirec_full_ce_bwd_f32(const float* S, int64_t B, const float* E, int64_t I,
-                                     int32_t d, const int64_t* target, const float* lse,
-                                     const float* g_dev, int32_t splits, float* gS, float* dE,
-                                     void* workspace, void* stream) {
+static int xe_bwd(const float* S, int64_t B, const int64_t* rows, const int32_t* n_dev,
+                  const float* E, int64_t I, int32_t d, const int64_t* target, const float* lse,
+                  const float* g_dev, int32_t splits, float* gS, float* dE, void* workspace,
+                  void* stream, const char* what) {
   if (B == 0) return 0;
   if (!S || !E || !target || !lse || !g_dev || !gS || !dE || !workspace || B < 0 || I <= 0) {
-    set_error("mirec_full_ce_bwd_f32: bad arguments");
+    set_error("%s: bad arguments", what);
     return -1;
   }
   int64_t span;
@@ -390,14 +445,57 @@ extern "C" int mirec_full_ce_bwd_f32(const float* S, int64_t B, const float* E, 
   const dim3 gi((unsigned)((I + 127) / 128));
   const int64_t qspan = (B + kXeTile - 1) / kXeTile * kXeTile;
   hipStream_t st = (hipStream_t)stream;
-  MIREC_XE_SWITCH("mirec_full_ce_bwd_f32", kXeQuery, gq, S, B, E, I, target, lse, g_dev, B,
-                  span, part, (float*)nullptr, (float*)nullptr, (float*)nullptr)
+  MIREC_XE_SWITCH(what, kXeQuery, gq, S, B, E, I, target, lse, g_dev, B, span, part,
+                  (float*)nullptr, (float*)nullptr, (float*)nullptr)
   if (ns > 1) {
     const int64_t n4 = B * d / 4;
     hipLaunchKernelGGL(xent_sum_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, n4,
-                       ns, (const float4*)part, (float4*)gS);
+                       ns, (const float4*)part, (float4*)gS, d / 4,
+                       rows ? n_dev : (const int32_t*)nullptr);
   }
-  MIREC_XE_SWITCH("mirec_full_ce_bwd_f32", kXeItem, gi, E, I, S, B, target, lse, g_dev, B, qspan,
-                  dE, (float*)nullptr, (float*)nullptr, (float*)nullptr)
-  return launch_status("mirec_full_ce_bwd_f32");
+  MIREC_XE_SWITCH(what, kXeItem, gi, E, I, S, B, target, lse, g_dev, B, qspan, dE,
+                  (float*)nullptr, (float*)nullptr, (float*)nullptr)
+  return launch_status(what);
+}
+
+extern "C" int mirec_full_ce_fwd_f32(const float* S, int64_t B, const float* E, int64_t I,
+                                     int32_t d, const int64_t* target, int32_t splits,
+                                     float* lse, float* loss_rows, void* workspace,
+                                     void* stream) {
+  return xe_fwd(S, B, nullptr, nullptr, E, I, d, target, splits, lse, loss_rows, workspace,
+                stream, "mirec_full_ce_fwd_f32");
+}
+
+extern "C" int mirec_full_ce_bwd_f32(const float* S, int64_t B, const float* E, int64_t I,
+                                     int32_t d, const int64_t* target, const float* lse,
+                                     const float* g_dev, int32_t splits, float* gS, float* dE,
+                                     void* workspace, void* stream) {
+  return xe_bwd(S, B, nullptr, nullptr, E, I, d, target, lse, g_dev, splits, gS, dE, workspace,
+                stream, "mirec_full_ce_bwd_f32");
+}
+
+extern "C" int mirec_rows_ce_fwd_f32(const float* X, int64_t n_x, const int64_t* row,
+                                          int64_t R, const int32_t* n_rows_dev, const float* E,
+                                          int64_t I, int32_t d, const int64_t* target,
+                                          int32_t splits, float* lse, float* loss_rows,
+                                          void* workspace, void* stream) {
+  if (R > 0 && (!row || n_x <= 0)) {
+    set_error("mirec_rows_ce_fwd_f32: bad arguments");
+    return -1;
+  }
+  return xe_fwd(X, R, row, n_rows_dev, E, I, d, target, splits, lse, loss_rows, workspace,
+                stream, "mirec_rows_ce_fwd_f32");
+}
+
+extern "C" int mirec_rows_ce_bwd_f32(const float* X, int64_t n_x, const int64_t* row,
+                                          int64_t R, const int32_t* n_rows_dev, const float* E,
+                                          int64_t I, int32_t d, const int64_t* target,
+                                          const float* lse, const float* g_dev, int32_t splits,
+                                          float* gS, float* dE, void* workspace, void* stream) {
+  if (R > 0 && (!row || n_x <= 0)) {
+    set_error("mirec_rows_ce_bwd_f32: bad arguments");
+    return -1;
+  }
+  return xe_bwd(X, R, row, n_rows_dev, E, I, d, target, lse, g_dev, splits, gS, dE, workspace,
+                stream, "mirec_rows_ce_bwd_f32");
 }

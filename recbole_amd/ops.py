@@ -1355,6 +1355,123 @@ def full_ce_bwd(S, E, target, lse, g, splits: int = 0):
     return gS, dE
 
 
+def _rows_ce_args(X, row, n_rows, E, target, what):
+    _dev(X, torch.float32, "X")
+    _dev(row, torch.int64, "row")
+    _dev(E, torch.float32, "E")
+    _dev(target, torch.int64, "target")
+    if n_rows is not None:
+        _dev(n_rows, torch.int32, "n_rows")
+    R, d = row.numel(), X.shape[1]
+    if X.dim() != 2 or E.shape[1] != d or target.numel() != R or (
+            n_rows is not None and n_rows.numel() != 1):
+        raise ValueError(f"{what}: shapes differ")
+    return R, d
+
+
+def full_ce_rows_fwd(X, row, target, E, n_rows=None, splits: int = 0):
+    """K12a over gathered rows (K17): (lse[R], loss_rows[R]) of the logits X[row] @ E^T against
+    `target`; only the first min(R, n_rows[0]) queries exist (n_rows: a one-element int32
+    device tensor, None = all R), later entries are exactly 0. row[r] of an existing query
+    must lie in [0, X.shape[0]) (not checked: no host sync)."""
+    R, d = _rows_ce_args(X, row, n_rows, E, target, "full_ce_rows_fwd")
+    lse = torch.empty(R, dtype=torch.float32, device=X.device)
+    loss_rows = torch.empty(R, dtype=torch.float32, device=X.device)
+    n = lib().mirec_full_ce_workspace_size(R, E.shape[0], d, splits)
+    ws = torch.empty(n, dtype=torch.uint8, device=X.device)
+    rc = lib().mirec_rows_ce_fwd_f32(ptr(X), X.shape[0], ptr(row), R, ptr(n_rows), ptr(E),
+                                     E.shape[0], d, ptr(target), splits, ptr(lse),
+                                     ptr(loss_rows), ptr(ws), stream_handle())
+    check(rc, "mirec_rows_ce_fwd_f32")
+    return lse, loss_rows
+
+
+def full_ce_rows_bwd(X, row, target, E, lse, g, n_rows=None, splits: int = 0, dE=None):
+    """K12b + K12c over gathered rows (K17): (gS[R, d] compact, dE[I, d]) with the factor
+    g[0] as it stands (the caller folds 1 / count in; no division by R); gS rows past the
+    count are exactly 0. dE: an [I, d] tensor to write into (e.g. the first rows of a larger
+    table gradient), allocated when None."""
+    R, d = _rows_ce_args(X, row, n_rows, E, target, "full_ce_rows_bwd")
+    _dev(lse, torch.float32, "lse")
+    _dev(g, torch.float32, "g")
+    if lse.numel() != R or g.numel() != 1:
+        raise ValueError("full_ce_rows_bwd: shapes differ")
+    gS = torch.empty(R, d, dtype=torch.float32, device=X.device)
+    if dE is None:                                                # every row written
+        dE = torch.empty(E.shape[0], d, dtype=torch.float32, device=X.device)
+    elif _dev(dE, torch.float32, "dE").shape != E.shape:
+        raise ValueError("full_ce_rows_bwd: dE must have E's shape")
+    n = lib().mirec_full_ce_workspace_size(R, E.shape[0], d, splits)
+    ws = torch.empty(n, dtype=torch.uint8, device=X.device)
+    rc = lib().mirec_rows_ce_bwd_f32(ptr(X), X.shape[0], ptr(row), R, ptr(n_rows), ptr(E),
+                                     E.shape[0], d, ptr(target), ptr(lse), ptr(g), splits,
+                                     ptr(gS), ptr(dE), ptr(ws), stream_handle())
+    check(rc, "mirec_rows_ce_bwd_f32")
+    return gS, dE
+
+
+# ---------------------------------------------------------------- K17 Cloze task (BERT4Rec)
+def cloze_mask(item_seq, M: int, n_items: int, mask_ratio: float, seed: int, counter,
+               negatives: bool = True):
+    """K17a: (masked_seq[B, L], pos_items[B, M], neg_items[B, M] or None, masked_index[B, M])
+    of BERT4Rec.reconstruct_train_data, drawn on the device from (seed, counter[0]). The
+    counter is only read: the caller advances it (counter.add_(1)) after the call."""
+    _dev(item_seq, torch.int64, "item_seq")
+    _dev(counter, torch.int64, "counter")
+    if item_seq.dim() != 2:
+        raise ValueError("cloze_mask: item_seq must be [B, L]")
+    B, L = item_seq.shape
+    if n_items - 1 <= L:
+        raise ValueError(f"cloze_mask: n_items - 1 = {n_items - 1} <= L = {L}: a negative "
+                         f"outside the row could not be drawn")
+    if not (1 <= M <= L <= 64):
+        raise ValueError(f"cloze_mask: needs 1 <= M <= L <= 64, got M = {M}, L = {L}")
+    dev = item_seq.device
+    masked_seq = torch.empty(B, L, dtype=torch.int64, device=dev)
+    pos = torch.empty(B, M, dtype=torch.int64, device=dev)
+    idx = torch.empty(B, M, dtype=torch.int64, device=dev)
+    neg = torch.empty(B, M, dtype=torch.int64, device=dev) if negatives else None
+    rc = lib().mirec_cloze_mask(ptr(item_seq), B, L, M, n_items, float(mask_ratio),
+                                seed & ((1 << 64) - 1), ptr(counter), ptr(masked_seq), ptr(pos),
+                                ptr(idx), ptr(neg), stream_handle())
+    check(rc, "mirec_cloze_mask")
+    return masked_seq, pos, neg, idx
+
+
+def cloze_compact(masked_index, pos_items, L: int):
+    """K17b: (act_row[B*M], act_target[B*M], n_act[1] int32, slot_of[B*L] int32): the slots
+    with masked_index > 0 in ascending (b, slot) order as rows b*L + index of the [B*L, d]
+    encoder output, and the inverse map (-1 elsewhere). One launch, no host sync."""
+    _dev(masked_index, torch.int64, "masked_index")
+    _dev(pos_items, torch.int64, "pos_items")
+    if masked_index.dim() != 2 or pos_items.shape != masked_index.shape:
+        raise ValueError("cloze_compact: masked_index and pos_items must be [B, M]")
+    B, M = masked_index.shape
+    dev = masked_index.device
+    act_row = torch.empty(B * M, dtype=torch.int64, device=dev)
+    act_target = torch.empty(B * M, dtype=torch.int64, device=dev)
+    n_act = torch.empty(1, dtype=torch.int32, device=dev)
+    slot_of = torch.empty(B * L, dtype=torch.int32, device=dev)
+    rc = lib().mirec_cloze_compact(ptr(masked_index), ptr(pos_items), B, L, M, ptr(act_row),
+                                   ptr(act_target), ptr(n_act), ptr(slot_of), stream_handle())
+    check(rc, "mirec_cloze_compact")
+    return act_row, act_target, n_act, slot_of
+
+
+def rows_from_slots(gS, slot_of):
+    """K17c: gX[p] = gS[slot_of[p]] where slot_of[p] >= 0, zeros elsewhere; [n_pos, d], every
+    element written once."""
+    _dev(gS, torch.float32, "gS")
+    _dev(slot_of, torch.int32, "slot_of")
+    if gS.dim() != 2:
+        raise ValueError("rows_from_slots: gS must be [R, d]")
+    n, d = slot_of.numel(), gS.shape[1]
+    gX = torch.empty(n, d, dtype=torch.float32, device=gS.device)
+    rc = lib().mirec_rows_from_slots_f32(ptr(gS), ptr(slot_of), n, d, ptr(gX), stream_handle())
+    check(rc, "mirec_rows_from_slots_f32")
+    return gX
+
+
 # ---------------------------------------------------------------- K7 graph propagation
 def _rows_ref(t):
     """mirec_rows_ref from None, a [n, d] tensor, or a (lo, hi) pair of row blocks."""

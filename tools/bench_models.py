@@ -35,6 +35,12 @@ C2 headline (bench.py): one JSON line per configuration, 1 GPU.
       cat, gathers) on the same device, weights and batches: ms/step and peak allocated of
       both over alternating timed windows, and the two steps' loss and gradients compared
       with the dropout off. Not in the default list: --configs G2.
+  B3  BERT4Rec: 65,536 items + PAD, L = 50, d = 128, 2 layers, 2 heads, B = 1,024,
+      mask_ratio 0.2 (M = 10), loss 'CE', run eagerly: steps/s with ce_kernel 'fused'
+      (K17b + K12 over the masked rows + K17c) and 'library' (the reference's op sequence,
+      a [B, M, n_items] logits tensor), the peak allocated memory of both, K17a alone (HIP
+      events) and the wall time of the reference's host masking loop restated here in pure
+      Python on the same batch. Not in the default list: --configs B3.
 
 Synthetic data (seeded numpy PCG64 / torch generators), random init. Each step is
 the Trainer's generic step: zero_grad -> calculate_loss -> backward -> FusedAdam.
@@ -833,6 +839,128 @@ def bench_multivae(dev, steps, warmup, scale=1.0, B=2048, K=10, generic_users=25
     }
 
 
+def _reference_cloze_loop(item_seq, mask_ratio, M, n_items, mask_token):
+    """BERT4Rec.reconstruct_train_data as the reference runs it (bert4rec.py:111-156): the
+    batch copied to the host, Python lists, random.random() per position, a rejection-sampled
+    negative per masked item, four tensors built on the device. Returns them."""
+    import random
+
+    def pad(sequence, max_length):
+        sequence = [0] * (max_length - len(sequence)) + sequence
+        return sequence[-max_length:]
+    device = item_seq.device
+    batch_size = item_seq.size(0)
+    instances = item_seq.cpu().numpy().tolist()
+    seqs, poss, negs, idxs = [], [], [], []
+    for instance in instances:
+        masked_sequence = instance.copy()
+        pos_item, neg_item, index_ids = [], [], []
+        for index_id, item in enumerate(instance):
+            if item == 0:
+                break
+            if random.random() < mask_ratio:
+                pos_item.append(item)
+                neg = random.randint(1, n_items - 1)
+                while neg in instance:
+                    neg = random.randint(1, n_items - 1)
+                neg_item.append(neg)
+                masked_sequence[index_id] = mask_token
+                index_ids.append(index_id)
+        seqs.append(masked_sequence)
+        poss.append(pad(pos_item, M))
+        negs.append(pad(neg_item, M))
+        idxs.append(pad(index_ids, M))
+    return tuple(torch.tensor(x, dtype=torch.long, device=device).view(batch_size, -1)
+                 for x in (seqs, poss, negs, idxs))
+
+
+def bench_bert4rec(dev, steps, warmup, scale=1.0, B=1024, L=50, d=128, n_batches=8):
+    """B3: the BERT4Rec training step, ce_kernel 'fused' against 'library' on the same
+    weights and batches (each in its own timed window, peak memory reset between them), and
+    the Cloze masking alone: K17a against the reference's host loop."""
+    from recbole_amd import ops
+    from recbole_amd.config import Config
+    from recbole_amd.data.interaction import Interaction
+    from recbole_amd.model.sequential_recommender import BERT4Rec
+    from recbole_amd.trainer.optim import FusedAdam
+    from recbole_amd.utils import FeatureType
+    n_items = max(1000, int(65_536 * scale)) + 1
+    rng = np.random.default_rng(2020)
+    batches = []
+    for _ in range(n_batches):
+        lens = np.minimum(rng.poisson(20, B) + 4, L).astype(np.int64)
+        seq = np.zeros((B, L), dtype=np.int64)
+        seq[np.arange(L)[None, :] < lens[:, None]] = _zipf_ids(rng, 1.1, int(lens.sum()),
+                                                               n_items - 1)
+        batches.append(Interaction({'item_id_list': torch.as_tensor(seq),
+                                    'item_length': torch.as_tensor(lens)}).to(dev))
+    state, out = None, {}
+    for kernel in ('fused', 'library'):
+        config = Config(model='BERT4Rec', dataset='b3-synth', config_dict={
+            'hidden_size': d, 'n_heads': 2, 'inner_size': 256, 'MAX_ITEM_LIST_LENGTH': L,
+            'mask_ratio': 0.2, 'loss_type': 'CE', 'ce_kernel': kernel,
+            'training_neg_sample_num': 0, 'state': 'ERROR', 'data_path': ROOT,
+            'load_col': None})
+        config['device'] = dev
+        torch.manual_seed(2020)
+        model = BERT4Rec(config, StubDataset({'item_id': FeatureType.TOKEN},
+                                             {'item_id': n_items})).to(dev)
+        if state is None:
+            state = {k: v.clone() for k, v in model.state_dict().items()}
+        model.load_state_dict(state)
+        opt = FusedAdam(model.parameters(), lr=1e-3)
+        it = [0]
+
+        def step():
+            b = batches[it[0] % n_batches]
+            it[0] += 1
+            opt.zero_grad()
+            loss_ = model.calculate_loss(b)
+            loss_.backward()
+            opt.step()
+            return loss_
+
+        torch.cuda.empty_cache()
+        torch.cuda.reset_peak_memory_stats(dev)
+        t = _timed(step, steps, warmup, opt)
+        out[kernel] = {'steps_per_s': round(1.0 / t, 2), 'ms_per_step': round(t * 1e3, 3),
+                       'sequences_per_s': round(B / t, 1),
+                       'peak_allocated_MB': round(torch.cuda.max_memory_allocated(dev) / 1e6, 1),
+                       'last_loss': round(float(step().item()), 4)}
+        M, ratio = model.mask_item_length, model.mask_ratio
+        del model, opt
+    seq0 = batches[0]['item_id_list']
+    counter = torch.zeros(1, dtype=torch.int64, device=dev)
+    k17a = _event_time(lambda: ops.cloze_mask(seq0, M, n_items, ratio, 2020, counter, False))
+    k17a_neg = _event_time(lambda: ops.cloze_mask(seq0, M, n_items, ratio, 2020, counter, True))
+    host = []
+    for _ in range(3):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        _reference_cloze_loop(seq0, ratio, M, n_items, n_items)
+        torch.cuda.synchronize()
+        host.append(time.perf_counter() - t0)
+    return {
+        'config': 'B3', 'model': 'BERT4Rec', 'metric': 'train steps/s (ce_kernel fused)',
+        'value': out['fused']['steps_per_s'], 'unit': 'steps/s', 'batch': B, 'steps': steps,
+        'fused': out['fused'], 'library': out['library'],
+        'fused_over_library': round(out['library']['ms_per_step'] / out['fused']['ms_per_step'],
+                                    3),
+        'library_logits_MB': round(B * M * n_items * 4 / 1e6, 1),
+        'cloze_mask': {
+            'k17a_us': round(k17a * 1e6, 1), 'k17a_with_negatives_us': round(k17a_neg * 1e6, 1),
+            'reference_host_loop_ms': round(float(np.median(host)) * 1e3, 2),
+            'timing': 'K17a: HIP events around one ops.cloze_mask (the launch and its four '
+                      'output allocations), median of 10; host loop: wall time of the '
+                      "reference's reconstruct_train_data restated in pure Python on the same "
+                      'batch (device -> host copy, loop, four tensors back), median of 3'},
+        'workload': f'BERT4Rec: {n_items:,} items (incl. PAD) + mask token, L={L}, d={d}, '
+                    f'2 layers, 2 heads, inner 256, dropout 0.5, mask_ratio 0.2 (M={M}), '
+                    f'dense Adam, eager step',
+        'dtype': 'fp32', 'data': 'synthetic (Zipf(1.1) items, Poisson(20)+4 lengths, seeded)',
+    }
+
+
 def _c3_ce_record(dev, step, opt, model, batches, loss, steps, warmup, n_items, B, L, d):
     """The C3 step with the full-catalogue cross entropy: sequences/s, the peak allocated
     memory of the run (measured before the loss-only timings below), and the loss's own forward / backward call times (HIP
@@ -1165,6 +1293,8 @@ def main():
             r = bench_multivae(dev, args.steps, args.warmup, args.scale)
         elif c == 'G2':
             r = bench_ngcf(dev, args.steps, args.warmup, args.scale)
+        elif c == 'B3':
+            r = bench_bert4rec(dev, args.steps, args.warmup, args.scale)
         else:
             raise SystemExit(f'unknown config {c}')
         print(json.dumps(r), flush=True)
