@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define MIREC_ABI_VERSION 24
+#define MIREC_ABI_VERSION 25
 
 int mirec_abi_version(void);
 const char* mirec_last_error(void);
@@ -924,6 +924,18 @@ int mirec_ctx_fm_bwd_f32(const mirec_ctx_field* fields_dev, int32_t n_fields, in
                          int32_t d, const float* concat, const float* g_concat,
                          const float* g_fm, const float* work, void* stream);
 
+/* K8 without the FM term (xDeepFM, xdeepfm.py:182: the score has the first-order term only):
+ * the same fields, concat, keys, work buffer and per-contribution gradients as
+ * mirec_ctx_fm_*, with y_lin[b] = (sum float w*x + sum token w + sum token_seq masked w)
+ * + bias[0] and ge = g_concat in the backward (g_lin takes g_fm's place for the first-order
+ * gradients). The S part of work is neither written nor read. */
+int mirec_ctx_linear_fwd_f32(const mirec_ctx_field* fields_dev, int32_t n_fields, int64_t B,
+                             int32_t d, const float* bias, float* concat, float* y_lin,
+                             float* work, void* stream);
+int mirec_ctx_linear_bwd_f32(const mirec_ctx_field* fields_dev, int32_t n_fields, int64_t B,
+                             int32_t d, const float* concat, const float* g_concat,
+                             const float* g_lin, const float* work, void* stream);
+
 /* sigmoid + nn.BCELoss (DeepFM.forward / calculate_loss, deepfm.py:66-73):
  * z = y_fm + y_deep (y_deep may be NULL); prob = sigmoid(z);
  * loss[b] = (t-1)*max(log(1-p),-100) - t*max(log p,-100)  (mean = sum/B);
@@ -1500,6 +1512,49 @@ int mirec_ngcf_layer_bwd_f32(const mirec_rows_ld* G, const mirec_rows_ld* E_next
 int32_t mirec_ngcf_wgrad_splits(int64_t n);
 int mirec_ngcf_wgrad_f32(const float* gz, const mirec_rows_ld* E, const float* x, int64_t n,
                          int32_t d_in, int32_t d_out, float* partials, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * K18 — xDeepFM's Compressed Interaction Network (csrc/cin.hip; reference
+ * xdeepfm.py:116-169). One layer over X0 [B, m, D], Xk [B, H, D] (layer 0: Xk = X0, H = m),
+ * W [N, H m] row-major (column h m + j) and b [N]:
+ *   out[b, n, d] = b[n] + sum_h sum_j W[n, h m + j] Xk[b, h, d] X0[b, j, d]
+ * out is never stored. Channels [0, n_hid) are X_{k+1} [B, n_hid, D]; channels [dir0, N)
+ * are summed over d into pooled[b, pool_off + n - dir0] (row stride pool_ld). direct: True
+ * is (n_hid, dir0) = (N, 0), direct: False (N/2, N/2), the last layer (0, 0) in both.
+ * Built shapes (mirec_cin_shape_ok): 2 <= m <= 64, 1 <= H <= 256, 1 <= D <= 64,
+ * 2 <= N <= 256; anything else is an error. No alignment is asked of any operand.
+ *
+ * forward:  writes Xn (n_hid > 0) and the layer's pooled columns.
+ * backward: G[b, n, d] = dXn[b, n, d] (n < n_hid; dXn NULL: 0) + g_pooled[b, pool_off +
+ *           n - dir0] (n >= dir0). T = G W per (b, d) row stays in registers:
+ *           dXk[b, h, d] = sum_j T X0[b, j, d];  dX0[b, j, d] (+)= sum_h T Xk[b, h, d]
+ *           (accumulate != 0 adds to dX0, else it is written). dXk NULL is layer 0
+ *           (Xk == X0): both terms go to dX0.
+ * wgrad:    partials [mirec_cin_wgrad_splits(B, m, H, D), mirec_cin_wgrad_stride(N, H m)]:
+ *           split s's rows' sum, rows in order, of dW [N, H m] (floats [0, N H m)) and
+ *           db [N] (from float round_up(N H m, 4)); mirec_linear_grad_finish_f32 adds the
+ *           splits in order. At most 32 splits whatever B is.
+ * Every result is the same bits run to run and for any grid cap.
+ * ------------------------------------------------------------------------- */
+/* mirec_cin_grid_cap(w): as mirec_ngcf_grid_cap, for the two persistent kernels (forward,
+ * backward). */
+int32_t mirec_cin_grid_cap(int32_t workgroups);
+int mirec_cin_shape_ok(int32_t m, int32_t H, int32_t D, int32_t N);
+int mirec_cin_layer_fwd_f32(const float* X0, const float* Xk, int64_t B, int32_t m, int32_t H,
+                            int32_t D, const float* W, const float* b, int32_t N, int32_t n_hid,
+                            int32_t dir0, float* Xn, float* pooled, int32_t pool_off,
+                            int32_t pool_ld, void* stream);
+int mirec_cin_layer_bwd_f32(const float* X0, const float* Xk, int64_t B, int32_t m, int32_t H,
+                            int32_t D, const float* W, int32_t N, int32_t n_hid, int32_t dir0,
+                            const float* dXn, const float* g_pooled, int32_t pool_off,
+                            int32_t pool_ld, float* dXk, float* dX0, int32_t accumulate,
+                            void* stream);
+int32_t mirec_cin_wgrad_splits(int64_t B, int32_t m, int32_t H, int32_t D);
+int64_t mirec_cin_wgrad_stride(int32_t N, int32_t K);
+int mirec_cin_wgrad_f32(const float* X0, const float* Xk, int64_t B, int32_t m, int32_t H,
+                        int32_t D, int32_t N, int32_t n_hid, int32_t dir0, const float* dXn,
+                        const float* g_pooled, int32_t pool_off, int32_t pool_ld,
+                        float* partials, void* stream);
 
 #ifdef __cplusplus
 }

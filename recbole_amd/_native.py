@@ -351,9 +351,23 @@ SIGNATURES = {
     "mirec_ngcf_wgrad_splits": (c_int32, [c_int64]),
     "mirec_ngcf_wgrad_f32": (c_int, [_P, ctypes.POINTER(RowsLd), _P, c_int64, c_int32, c_int32,
                                      _P, _P]),
+    "mirec_ctx_linear_fwd_f32": (c_int, [_P, c_int32, c_int64, c_int32, _P, _P, _P, _P, _P]),
+    "mirec_ctx_linear_bwd_f32": (c_int, [_P, c_int32, c_int64, c_int32, _P, _P, _P, _P, _P]),
+    "mirec_cin_grid_cap": (c_int32, [c_int32]),
+    "mirec_cin_shape_ok": (c_int, [c_int32, c_int32, c_int32, c_int32]),
+    "mirec_cin_layer_fwd_f32": (c_int, [_P, _P, c_int64, c_int32, c_int32, c_int32, _P, _P,
+                                        c_int32, c_int32, c_int32, _P, _P, c_int32, c_int32,
+                                        _P]),
+    "mirec_cin_layer_bwd_f32": (c_int, [_P, _P, c_int64, c_int32, c_int32, c_int32, _P, c_int32,
+                                        c_int32, c_int32, _P, _P, c_int32, c_int32, _P, _P,
+                                        c_int32, _P]),
+    "mirec_cin_wgrad_splits": (c_int32, [c_int64, c_int32, c_int32, c_int32]),
+    "mirec_cin_wgrad_stride": (c_int64, [c_int32, c_int32]),
+    "mirec_cin_wgrad_f32": (c_int, [_P, _P, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                    c_int32, _P, _P, c_int32, c_int32, _P, _P]),
 }
 
-ABI_VERSION = 24
+ABI_VERSION = 25
 
 
 class NativeError(RuntimeError):

@@ -1,6 +1,7 @@
 """Default configuration values, restated as Python data from the reference's
 property files (recbole/properties/overall.yaml, dataset/sample.yaml,
-dataset/ml-100k.yaml, model/{BPR,LightGCN,NGCF,SASRec,GRU4Rec,BERT4Rec,DeepFM,NeuMF,MultiDAE,MultiVAE}.yaml,
+dataset/ml-100k.yaml, model/{BPR,LightGCN,NGCF,SASRec,GRU4Rec,BERT4Rec,DeepFM,xDeepFM,NeuMF,MultiDAE,
+MultiVAE}.yaml,
 quick_start_config/{sequential,context-aware}.yaml)."""
 from recbole_amd.utils.enum_type import ModelType
 
@@ -69,6 +70,10 @@ MODEL_DEFAULTS = {
                      layer_norm_eps=1e-12, initializer_range=0.02, mask_ratio=0.2,
                      loss_type='CE', ce_kernel='library'),
     'DeepFM': dict(embedding_size=10, mlp_hidden_size=[128, 128, 128], dropout_prob=0.2),
+    # cin_kernel: the build's key ('fused' = K18, 'library' = the reference's op sequence)
+    'xDeepFM': dict(embedding_size=10, mlp_hidden_size=[128, 128, 128], reg_weight=5e-4,
+                    dropout_prob=0.2, direct=False, cin_layer_size=[100, 100, 100],
+                    cin_kernel='fused'),
     'NeuMF': dict(mf_embedding_size=64, mlp_embedding_size=64, mlp_hidden_size=[128, 64, 32],
                   dropout_prob=0.0, weight_decay=1e-08, mf_train=True, mlp_train=True,
                   valid_metric='HIT@10', use_pretrain=False, mf_pretrain_path=None,

@@ -44,7 +44,9 @@ __device__ __forceinline__ int64_t clamp_row(int64_t r, int64_t n) {
 // term -> fo[b, f], the token row id -> keys. Every (sample, field) pair is independent:
 // B * F groups in flight instead of B. (2) reduce, LPS lanes per sample: the FM sums
 // S = sum_f e, Q = sum_f e^2 and the first-order sums by kind, all in field order (the
-// one-kernel order), y_fm; S is kept for the backward.
+// one-kernel order), y_fm; S is kept for the backward. FM = false (xDeepFM and the other
+// models without a second-order term, mirec_ctx_linear_*): the reduce forms only the
+// first-order sums and the backward's field gradient is g_concat alone; fm_sum is not touched.
 template <int LPS>
 __global__ __launch_bounds__(kCtxThreads) void ctx_fm_gather_kernel(
     const mirec_ctx_field* __restrict__ fields, int n_fields, int64_t B, int d,
@@ -85,7 +87,7 @@ __global__ __launch_bounds__(kCtxThreads) void ctx_fm_gather_kernel(
   if (k == 0) fo[b * F + f] = w1;
 }
 
-template <int LPS>
+template <int LPS, bool FM>
 __global__ __launch_bounds__(kCtxThreads) void ctx_fm_reduce_kernel(
     const mirec_ctx_field* __restrict__ fields, int n_fields, int64_t B, int d,
     const float* __restrict__ bias, const float* __restrict__ concat,
@@ -109,7 +111,7 @@ __global__ __launch_bounds__(kCtxThreads) void ctx_fm_reduce_kernel(
       const int f = f0 + j;
       const bool ok = f < n_fields;
       kind[j] = ok ? fields[f].kind : -1;
-      e[j] = ok && col ? concat[(b * F + f) * d + k] : 0.f;
+      e[j] = FM && ok && col ? concat[(b * F + f) * d + k] : 0.f;
       w1[j] = ok ? fo[b * F + f] : 0.f;
     }
 #pragma unroll
@@ -118,9 +120,15 @@ __global__ __launch_bounds__(kCtxThreads) void ctx_fm_reduce_kernel(
       if (kind[j] == 0) fo_tok += w1[j];
       else if (kind[j] == 1) fo_seq += w1[j];
       else fo_float += w1[j];
-      S += e[j];
-      Q += e[j] * e[j];
+      if (FM) {
+        S += e[j];
+        Q += e[j] * e[j];
+      }
     }
+  }
+  if (!FM) {
+    if (k == 0) y_fm[b] = ((fo_float + fo_tok) + fo_seq) + bias[0];
+    return;
   }
   if (col) fm_sum[b * d + k] = S;
   const float fm = 0.5f * group_sum<LPS>(col ? S * S - Q : 0.f);
@@ -130,7 +138,7 @@ __global__ __launch_bounds__(kCtxThreads) void ctx_fm_reduce_kernel(
 // Backward, one block row per field as the gather. g_concat: dL/d concat [B, F*d] (may
 // be NULL = 0); g_fm: dL/d y_fm [B]; fm_sum: the forward's S.
 // grad_e = g_concat + g_fm * (S_k - e) (d fm / d e_fk = S_k - e_fk).
-template <int LPS>
+template <int LPS, bool FM>
 __global__ __launch_bounds__(kCtxThreads) void ctx_fm_bwd_kernel(
     const mirec_ctx_field* __restrict__ fields, int n_fields, int64_t B, int d,
     const float* __restrict__ concat, const float* __restrict__ g_concat,
@@ -148,7 +156,8 @@ __global__ __launch_bounds__(kCtxThreads) void ctx_fm_bwd_kernel(
   float ge = 0.f;
   if (col) {
     const int64_t c = (b * F + f) * d + k;
-    ge = (g_concat ? g_concat[c] : 0.f) + gf * (fm_sum[b * d + k] - concat[c]);
+    ge = g_concat ? g_concat[c] : 0.f;
+    if (FM) ge += gf * (fm_sum[b * d + k] - concat[c]);
   }
   if (fd.kind == 0) {
     if (col && fd.grad) fd.grad[b * fd.grad_ld + k] = ge;
@@ -472,24 +481,28 @@ static unsigned ctx_grid(int64_t B, int lps) {
 
 using namespace mirec;
 
+// KERNEL(L): the instantiation for L lanes per sample
+#define MIREC_CTX_GATHER(L) ctx_fm_gather_kernel<L>
+#define MIREC_CTX_REDUCE(L) (ctx_fm_reduce_kernel<L, FM>)
+#define MIREC_CTX_BWD(L) (ctx_fm_bwd_kernel<L, FM>)
 #define MIREC_CTX_DISPATCH(KERNEL, NY, ...)                                                   \
   do {                                                                                        \
     hipStream_t st = (hipStream_t)stream;                                                     \
     const unsigned ny = (unsigned)(NY);                                                       \
     if (d <= 4)                                                                               \
-      hipLaunchKernelGGL(KERNEL<4>, dim3(ctx_grid(B, 4), ny), dim3(kCtxThreads), 0, st,       \
+      hipLaunchKernelGGL(KERNEL(4), dim3(ctx_grid(B, 4), ny), dim3(kCtxThreads), 0, st,       \
                          __VA_ARGS__);                                                        \
     else if (d <= 8)                                                                          \
-      hipLaunchKernelGGL(KERNEL<8>, dim3(ctx_grid(B, 8), ny), dim3(kCtxThreads), 0, st,       \
+      hipLaunchKernelGGL(KERNEL(8), dim3(ctx_grid(B, 8), ny), dim3(kCtxThreads), 0, st,       \
                          __VA_ARGS__);                                                        \
     else if (d <= 16)                                                                         \
-      hipLaunchKernelGGL(KERNEL<16>, dim3(ctx_grid(B, 16), ny), dim3(kCtxThreads), 0, st,     \
+      hipLaunchKernelGGL(KERNEL(16), dim3(ctx_grid(B, 16), ny), dim3(kCtxThreads), 0, st,     \
                          __VA_ARGS__);                                                        \
     else if (d <= 32)                                                                         \
-      hipLaunchKernelGGL(KERNEL<32>, dim3(ctx_grid(B, 32), ny), dim3(kCtxThreads), 0, st,     \
+      hipLaunchKernelGGL(KERNEL(32), dim3(ctx_grid(B, 32), ny), dim3(kCtxThreads), 0, st,     \
                          __VA_ARGS__);                                                        \
     else                                                                                      \
-      hipLaunchKernelGGL(KERNEL<64>, dim3(ctx_grid(B, 64), ny), dim3(kCtxThreads), 0, st,     \
+      hipLaunchKernelGGL(KERNEL(64), dim3(ctx_grid(B, 64), ny), dim3(kCtxThreads), 0, st,     \
                          __VA_ARGS__);                                                        \
   } while (0)
 
@@ -497,38 +510,71 @@ extern "C" size_t mirec_ctx_fm_work_floats(int64_t B, int32_t n_fields, int32_t 
   return B < 0 || n_fields < 0 || d < 0 ? 0 : (size_t)B * ((size_t)n_fields + (size_t)d);
 }
 
-extern "C" int mirec_ctx_fm_fwd_f32(const mirec_ctx_field* fields_dev, int32_t n_fields,
-                                    int64_t B, int32_t d, const float* bias, float* concat,
-                                    float* y_fm, float* work, void* stream) {
+template <bool FM>
+static int ctx_fwd(const char* what, const mirec_ctx_field* fields_dev, int32_t n_fields,
+                   int64_t B, int32_t d, const float* bias, float* concat, float* y, float* work,
+                   void* stream) {
   if (B == 0) return 0;
   if (!fields_dev || n_fields <= 0 || n_fields > 65535 || B < 0 || d < 1 || d > 64 || !bias ||
-      !concat || !y_fm || !work) {
-    set_error("mirec_ctx_fm_fwd_f32: bad arguments (1 <= d <= 64, 1 <= fields <= 65535)");
+      !concat || !y || !work) {
+    set_error("%s: bad arguments (1 <= d <= 64, 1 <= fields <= 65535)", what);
     return -1;
   }
   float* fo = work;
   float* fm_sum = work + B * n_fields;
-  MIREC_CTX_DISPATCH(ctx_fm_gather_kernel, n_fields, fields_dev, n_fields, B, d, concat, fo);
-  const int rc = launch_status("mirec_ctx_fm_fwd_f32: gather");
+  MIREC_CTX_DISPATCH(MIREC_CTX_GATHER, n_fields, fields_dev, n_fields, B, d, concat, fo);
+  const int rc = launch_status(what);
   if (rc) return rc;
-  MIREC_CTX_DISPATCH(ctx_fm_reduce_kernel, 1, fields_dev, n_fields, B, d, bias, concat, fo, y_fm,
+  MIREC_CTX_DISPATCH(MIREC_CTX_REDUCE, 1, fields_dev, n_fields, B, d, bias, concat, fo, y,
                      fm_sum);
-  return launch_status("mirec_ctx_fm_fwd_f32");
+  return launch_status(what);
+}
+
+template <bool FM>
+static int ctx_bwd(const char* what, const mirec_ctx_field* fields_dev, int32_t n_fields,
+                   int64_t B, int32_t d, const float* concat, const float* g_concat,
+                   const float* g_y, const float* work, void* stream) {
+  if (B == 0) return 0;
+  if (!fields_dev || n_fields <= 0 || n_fields > 65535 || B < 0 || d < 1 || d > 64 || !concat ||
+      !g_y || !work) {
+    set_error("%s: bad arguments (1 <= d <= 64, 1 <= fields <= 65535)", what);
+    return -1;
+  }
+  MIREC_CTX_DISPATCH(MIREC_CTX_BWD, n_fields, fields_dev, n_fields, B, d, concat, g_concat, g_y,
+                     work + B * n_fields);
+  return launch_status(what);
+}
+
+extern "C" int mirec_ctx_fm_fwd_f32(const mirec_ctx_field* fields_dev, int32_t n_fields,
+                                    int64_t B, int32_t d, const float* bias, float* concat,
+                                    float* y_fm, float* work, void* stream) {
+  return ctx_fwd<true>("mirec_ctx_fm_fwd_f32", fields_dev, n_fields, B, d, bias, concat, y_fm,
+                       work, stream);
 }
 
 extern "C" int mirec_ctx_fm_bwd_f32(const mirec_ctx_field* fields_dev, int32_t n_fields,
                                     int64_t B, int32_t d, const float* concat,
                                     const float* g_concat, const float* g_fm, const float* work,
                                     void* stream) {
-  if (B == 0) return 0;
-  if (!fields_dev || n_fields <= 0 || n_fields > 65535 || B < 0 || d < 1 || d > 64 || !concat ||
-      !g_fm || !work) {
-    set_error("mirec_ctx_fm_bwd_f32: bad arguments (1 <= d <= 64, 1 <= fields <= 65535)");
-    return -1;
-  }
-  MIREC_CTX_DISPATCH(ctx_fm_bwd_kernel, n_fields, fields_dev, n_fields, B, d, concat, g_concat,
-                     g_fm, work + B * n_fields);
-  return launch_status("mirec_ctx_fm_bwd_f32");
+  return ctx_bwd<true>("mirec_ctx_fm_bwd_f32", fields_dev, n_fields, B, d, concat, g_concat,
+                       g_fm, work, stream);
+}
+
+// The first-order-only form: y_lin = first-order sums + bias, no FM term (same work buffer;
+// its S part stays unwritten and unread).
+extern "C" int mirec_ctx_linear_fwd_f32(const mirec_ctx_field* fields_dev, int32_t n_fields,
+                                        int64_t B, int32_t d, const float* bias, float* concat,
+                                        float* y_lin, float* work, void* stream) {
+  return ctx_fwd<false>("mirec_ctx_linear_fwd_f32", fields_dev, n_fields, B, d, bias, concat,
+                        y_lin, work, stream);
+}
+
+extern "C" int mirec_ctx_linear_bwd_f32(const mirec_ctx_field* fields_dev, int32_t n_fields,
+                                        int64_t B, int32_t d, const float* concat,
+                                        const float* g_concat, const float* g_lin,
+                                        const float* work, void* stream) {
+  return ctx_bwd<false>("mirec_ctx_linear_bwd_f32", fields_dev, n_fields, B, d, concat, g_concat,
+                        g_lin, work, stream);
 }
 
 // The loss and its gradient in one launch for the training step: one 1024-lane block,

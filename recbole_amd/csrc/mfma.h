@@ -1,5 +1,6 @@
 // The fp32 MFMA tile every model kernel shares: the accumulator types, the two intrinsics
-// and K11's weight-in-LDS slab product (linear.hip; K16 in ngcf.hip runs the same loop).
+// and K11's weight-in-LDS slab product (linear.hip; K16 in ngcf.hip and K18 in cin.hip run
+// the same loop).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -48,13 +49,15 @@ __device__ __forceinline__ float4 load_float4(lds_floats p) {
 // are issued before this group's MFMAs, so their LDS latency passes under the products; the
 // GA accumulators are interleaved, so a dependent MFMA follows its predecessor GA issues
 // later.
+//
+// mfma_slab_acc adds the products to acc as it stands (K18's forward walks many weight slabs
+// into one set of accumulators); mfma_slab starts from zero.
 template <int NU, int NC, int KP, int GW = 4, typename BsPtr>
-__device__ __forceinline__ void mfma_slab(const float4 (&a)[NU], BsPtr Bs, int li, int lk,
-                                          floatx4 (&acc)[NC]) {
+__device__ __forceinline__ void mfma_slab_acc(const float4 (&a)[NU], BsPtr Bs, int li, int lk,
+                                              floatx4 (&acc)[NC]) {
   constexpr int GA = NC < GW ? NC : GW;
   constexpr int NG = NU * (NC / GA);
-#pragma unroll
-  for (int c = 0; c < NC; ++c) acc[c] = floatx4{0.f, 0.f, 0.f, 0.f};
+  static_assert(NC % GA == 0, "the column tiles come in whole groups");
   auto load_b = [&](float4 (&b)[GA], int g) {
     const int u = g / (NC / GA), cg = GA * (g % (NC / GA));
 #pragma unroll
@@ -83,6 +86,14 @@ __device__ __forceinline__ void mfma_slab(const float4 (&a)[NU], BsPtr Bs, int l
 #pragma unroll
       for (int c = 0; c < GA; ++c) bc[c] = bn[c];
   }
+}
+
+template <int NU, int NC, int KP, int GW = 4, typename BsPtr>
+__device__ __forceinline__ void mfma_slab(const float4 (&a)[NU], BsPtr Bs, int li, int lk,
+                                          floatx4 (&acc)[NC]) {
+#pragma unroll
+  for (int c = 0; c < NC; ++c) acc[c] = floatx4{0.f, 0.f, 0.f, 0.f};
+  mfma_slab_acc<NU, NC, KP, GW>(a, Bs, li, lk, acc);
 }
 
 }  // namespace mirec

@@ -9,6 +9,7 @@ uses when present:
 from logging import getLogger
 
 import numpy as np
+import torch
 import torch.nn as nn
 
 from recbole_amd.utils import InputType, ModelType
@@ -109,6 +110,39 @@ class ContextRecommender(AbstractRecommender):
         from recbole_amd.model.context import _CtxFMFn
         T, T1, Ef, Ef1, bias, seq, seq1 = self._fm_params()
         return _CtxFMFn.apply(self.field_layout, interaction, T, T1, Ef, Ef1, bias, *seq, *seq1)
+
+    def linear_fields(self, interaction):
+        """(concat [B, num_feature_field, d], y_first_order [B]) via K8's first-order form
+        (no FM term: xDeepFM's score, xdeepfm.py:182), differentiable; the same deferred
+        catch-up and stash as fm_fields."""
+        from recbole_amd.model.context import _CtxLinearFn
+        T, T1, Ef, Ef1, bias, seq, seq1 = self._fm_params()
+        return _CtxLinearFn.apply(self.field_layout, interaction, T, T1, Ef, Ef1, bias, *seq,
+                                  *seq1)
+
+    def linear_fields_torch(self, interaction):
+        """linear_fields as torch ops, for a CPU device (abstract_recommender.py:199-272,
+        layers.py:1029-1062): token rows through the offset table, token_seq fields as masked
+        means sum(mask e) / (count + 1e-8) with masked first-order sums, float fields as
+        E_f[j] x_j; concatenated [token | token_seq | float]."""
+        T, T1, Ef, Ef1, bias, seq, seq1 = self._fm_params()
+        rows, first = [], bias.new_zeros(())
+        if self.token_field_names:
+            ids = torch.stack([interaction[n].long() for n in self.token_field_names], dim=1)
+            ids = ids + torch.as_tensor(self.token_field_offsets, device=ids.device)
+            rows.append(T[ids])
+            first = first + T1[ids].sum(dim=(1, 2))
+        for name, E, E1 in zip(self.token_seq_field_names, seq, seq1):
+            ids = interaction[name].long()
+            mask = (ids != 0).to(E.dtype)
+            cnt = mask.sum(dim=1, keepdim=True)
+            rows.append(((E[ids] * mask.unsqueeze(2)).sum(dim=1) / (cnt + 1e-8)).unsqueeze(1))
+            first = first + (E1[ids].squeeze(2) * mask).sum(dim=1)
+        if self.float_field_names:
+            x = torch.stack([interaction[n].to(Ef.dtype) for n in self.float_field_names], dim=1)
+            rows.append(Ef.unsqueeze(0) * x.unsqueeze(2))
+            first = first + (Ef1.squeeze(1).unsqueeze(0) * x).sum(dim=1)
+        return torch.cat(rows, dim=1), first + bias
 
     def concat_embed_input_fields(self, interaction):
         """[B, num_feature_field, d] (abstract_recommender.py:356-363)."""

@@ -4,6 +4,8 @@ _CtxFMFn:      field embeddings of a batch -> (concat [B, F, d], y_fm [B]) where
                y_fm = first-order term + FM second-order term; backward gives the
                dense gradients nn.Embedding(sparse=False) would (zero tables +
                K2-grouped, fixed-order scatter of the per-contribution rows).
+_CtxLinearFn:  the same with y = the first-order term alone (xDeepFM; K8's
+               mirec_ctx_linear_* entry points), one body shared with _CtxFMFn.
 _SigmoidBCEFn: mean BCE of sigmoid(y_fm + y_deep) (deepfm.py:66-73).
 """
 from __future__ import annotations
@@ -120,8 +122,8 @@ def _grad_buffers(layout, interaction, B, d, keys, dev):
             'seq1': [E(ids.numel(), 1) for ids in seq_ids]}
 
 
-def ctx_fm_forward(layout, interaction, tables, B, d, bias, keys=None, grads=None):
-    """K8 forward. grads (the backward's buffers, _grad_buffers): the field descriptors
+def ctx_fm_forward(layout, interaction, tables, B, d, bias, keys=None, grads=None, fm=True):
+    """K8 forward (fm=False: the first-order-only form). grads (the backward's buffers, _grad_buffers): the field descriptors
     then also carry the gradient pointers, so the backward reuses them (one descriptor
     upload per step instead of two)."""
     dev = bias.device
@@ -136,18 +138,22 @@ def ctx_fm_forward(layout, interaction, tables, B, d, bias, keys=None, grads=Non
     work = torch.empty(max(1, lib().mirec_ctx_fm_work_floats(B, layout.n_fields, d)),
                        dtype=torch.float32, device=dev)
     with ops.timed_launch('ctx_fm_fwd'):
-        rc = lib().mirec_ctx_fm_fwd_f32(ptr(fields_dev), layout.n_fields, B, d, ptr(bias),
-                                        ptr(concat), ptr(y_fm), ptr(work), stream_handle())
-    check(rc, "mirec_ctx_fm_fwd_f32")
+        fwd = lib().mirec_ctx_fm_fwd_f32 if fm else lib().mirec_ctx_linear_fwd_f32
+        rc = fwd(ptr(fields_dev), layout.n_fields, B, d, ptr(bias), ptr(concat), ptr(y_fm),
+                 ptr(work), stream_handle())
+    check(rc, "mirec_ctx_fm_fwd_f32" if fm else "mirec_ctx_linear_fwd_f32")
     keep.append(fields_dev)
     keep.append(work)
     return concat, y_fm, keep
 
 
 class _CtxFMFn(torch.autograd.Function):
+    """fm (a class constant): whether y carries the FM second-order term."""
+    fm = True
 
-    @staticmethod
-    def forward(ctx, layout, interaction, T, T1, Ef, Ef1, bias, *seq_tables):
+    @classmethod
+    def forward(cls, ctx, layout, interaction, T, T1, Ef, Ef1, bias, *seq_tables):
+        ctx.fm = cls.fm
         ns = len(layout.seq_names)
         seq, seq1 = list(seq_tables[:ns]), list(seq_tables[ns:])
         d = (T if T is not None else (Ef if Ef is not None else seq[0])).shape[1]
@@ -192,7 +198,7 @@ class _CtxFMFn(torch.autograd.Function):
         if any(ctx.needs_input_grad[2:]):
             grads = _grad_buffers(layout, interaction, B, d, keys, bias.device)
         concat, y_fm, keep = ctx_fm_forward(layout, interaction, tables, B, d, bias.detach(), keys,
-                                            grads)
+                                            grads, fm=ctx.fm)
         ctx.fm_work, ctx.fields_dev, ctx.grads, ctx.keep = keep[-1], keep[-2], grads, keep
         ctx.layout, ctx.interaction, ctx.tables, ctx.B, ctx.d = layout, interaction, tables, B, d
         ctx.deferred_T = T if h is not None else None
@@ -216,10 +222,10 @@ class _CtxFMFn(torch.autograd.Function):
         grads, fields_dev = ctx.grads, ctx.fields_dev    # descriptors of the forward
         gc = None if g_concat is None else g_concat.contiguous()
         with ops.timed_launch('ctx_fm_bwd'):
-            rc = lib().mirec_ctx_fm_bwd_f32(ptr(fields_dev), layout.n_fields, B, d, ptr(concat),
-                                            ptr(gc), ptr(g_fm), ptr(ctx.fm_work),
-                                            stream_handle())
-        check(rc, "mirec_ctx_fm_bwd_f32")
+            bwd = lib().mirec_ctx_fm_bwd_f32 if ctx.fm else lib().mirec_ctx_linear_bwd_f32
+            rc = bwd(ptr(fields_dev), layout.n_fields, B, d, ptr(concat), ptr(gc), ptr(g_fm),
+                     ptr(ctx.fm_work), stream_handle())
+        check(rc, "mirec_ctx_fm_bwd_f32" if ctx.fm else "mirec_ctx_linear_bwd_f32")
         dT = dT1 = dEf = dEf1 = None
         if nt:
             T = tables['T']
@@ -254,6 +260,11 @@ class _CtxFMFn(torch.autograd.Function):
                                                  torch.zeros_like(tables['seq1'][i])))
         ctx.keep = ctx.grads = ctx.fields_dev = None      # the forward's buffers: done
         return (None, None, dT, dT1, dEf, dEf1, dbias, *dseq, *dseq1)
+
+
+class _CtxLinearFn(_CtxFMFn):
+    """(concat, y_first_order): _CtxFMFn without the FM term."""
+    fm = False
 
 
 _UNIT = {}

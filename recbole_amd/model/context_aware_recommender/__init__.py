@@ -1,3 +1,4 @@
 from recbole_amd.model.context_aware_recommender.deepfm import DeepFM
+from recbole_amd.model.context_aware_recommender.xdeepfm import xDeepFM
 
-__all__ = ['DeepFM']
+__all__ = ['DeepFM', 'xDeepFM']

@@ -1742,3 +1742,121 @@ def ngcf_wgrad(gz, E, x, d_in: int):
                                              ptr(finish_ticket(dev, 'linear')), stream_handle()),
           "mirec_linear_grad_finish_f32")
     return dW[:, :d_in].contiguous(), dW[:, d_in:].contiguous(), db
+
+
+# ---------------------------------------------------------------- K18 xDeepFM CIN
+def cin_shape_ok(m: int, H: int, D: int, N: int) -> bool:
+    """Whether K18 is built for a layer of N channels over X0 [B, m, D], Xk [B, H, D]
+    (m 2..64, H 1..256, D 1..64, N 2..256)."""
+    return lib().mirec_cin_shape_ok(int(m), int(H), int(D), int(N)) != 0
+
+
+def cin_grid_cap(workgroups: int) -> int:
+    """Cap the workgroups of K18a / K18b at `workgroups` (0: the chip decides; negative: only
+    ask); returns the cap before the call. No output bit depends on it."""
+    return int(lib().mirec_cin_grid_cap(int(workgroups)))
+
+
+def _cin_operands(what, X0, Xk, N, n_hid, dir0, W=None, b=None):
+    _dev(X0, torch.float32, "X0")
+    _dev(Xk, torch.float32, "Xk")
+    if X0.dim() != 3 or Xk.dim() != 3 or Xk.shape[0] != X0.shape[0] or Xk.shape[2] != X0.shape[2]:
+        raise ValueError(f"{what}: X0 {tuple(X0.shape)} and Xk {tuple(Xk.shape)} must be "
+                         f"[B, m, D] and [B, H, D]")
+    B, m, D = X0.shape
+    H = Xk.shape[1]
+    if not cin_shape_ok(m, H, D, N):
+        raise NativeError(f"{what}: shape m {m}, H {H}, D {D}, N {N} not in the built set "
+                          f"(m 2..64, H 1..256, D 1..64, N 2..256)")
+    if not (0 <= n_hid <= N and 0 <= dir0 <= N):
+        raise ValueError(f"{what}: channel split ({n_hid}, {dir0}) outside [0, {N}]")
+    if W is not None:
+        _dev(W, torch.float32, "W")
+        if W.shape != (N, H * m):
+            raise ValueError(f"{what}: W shape {tuple(W.shape)} != {(N, H * m)}")
+    if b is not None:
+        _dev(b, torch.float32, "b")
+        if b.shape != (N,):
+            raise ValueError(f"{what}: b shape {tuple(b.shape)} != ({N},)")
+    return B, m, H, D
+
+
+def _cin_pooled(what, t, name, B, N, dir0, pool_off):
+    _dev(t, torch.float32, name)
+    if t.dim() != 2 or t.shape[0] != B or pool_off < 0 or pool_off + (N - dir0) > t.shape[1]:
+        raise ValueError(f"{what}: {name} {tuple(t.shape)} does not hold columns "
+                         f"[{pool_off}, {pool_off + N - dir0}) of {B} rows")
+    return t.shape[1]
+
+
+def cin_layer_fwd(X0, Xk, W, b, n_hid: int, dir0: int, pooled, pool_off: int):
+    """K18a: one CIN layer, out = b + W (Xk x X0) per (sample, dimension) row, never stored:
+    returns X_{k+1} = out[:, :n_hid] as [B, n_hid, D] (None when n_hid == 0) and writes
+    sum_d out[:, dir0:] into pooled[:, pool_off : pool_off + N - dir0]."""
+    N = W.shape[0] if isinstance(W, torch.Tensor) else 0
+    B, m, H, D = _cin_operands("cin_layer_fwd", X0, Xk, N, n_hid, dir0, W, b)
+    ld = _cin_pooled("cin_layer_fwd", pooled, "pooled", B, N, dir0, pool_off)
+    Xn = torch.empty(B, n_hid, D, dtype=torch.float32, device=X0.device) if n_hid else None
+    with timed_launch('cin_fwd'):
+        rc = lib().mirec_cin_layer_fwd_f32(ptr(X0), ptr(Xk), B, m, H, D, ptr(W), ptr(b), N, n_hid,
+                                           dir0, ptr(Xn), ptr(pooled), pool_off, ld,
+                                           stream_handle())
+    check(rc, "mirec_cin_layer_fwd_f32")
+    return Xn
+
+
+def cin_layer_bwd(X0, Xk, W, n_hid: int, dir0: int, dXn, g_pooled, pool_off: int, dX0,
+                  accumulate: bool, layer0: bool):
+    """K18b: the data gradients of one CIN layer from dXn [B, n_hid, D] (or None) and the
+    layer's columns of g_pooled. Returns dXk [B, H, D] (None for layer 0, whose Xk is X0) and
+    writes (accumulate: adds) the X0 term — for layer 0 both terms — into dX0."""
+    N = W.shape[0] if isinstance(W, torch.Tensor) else 0
+    B, m, H, D = _cin_operands("cin_layer_bwd", X0, Xk, N, n_hid, dir0, W)
+    ld = _cin_pooled("cin_layer_bwd", g_pooled, "g_pooled", B, N, dir0, pool_off)
+    _dev(dX0, torch.float32, "dX0")
+    if dX0.shape != X0.shape:
+        raise ValueError(f"cin_layer_bwd: dX0 shape {tuple(dX0.shape)} != {tuple(X0.shape)}")
+    if dXn is not None:
+        _dev(dXn, torch.float32, "dXn")
+        if dXn.shape != (B, n_hid, D):
+            raise ValueError(f"cin_layer_bwd: dXn shape {tuple(dXn.shape)} != {(B, n_hid, D)}")
+    if layer0 and (Xk.data_ptr() != X0.data_ptr() or H != m):
+        raise ValueError("cin_layer_bwd: layer 0 takes Xk = X0")
+    dXk = None if layer0 else torch.empty_like(Xk)
+    with timed_launch('cin_bwd'):
+        rc = lib().mirec_cin_layer_bwd_f32(ptr(X0), ptr(Xk), B, m, H, D, ptr(W), N, n_hid, dir0,
+                                           ptr(dXn), ptr(g_pooled), pool_off, ld, ptr(dXk),
+                                           ptr(dX0), 1 if accumulate else 0, stream_handle())
+    check(rc, "mirec_cin_layer_bwd_f32")
+    return dXk
+
+
+def cin_wgrad(X0, Xk, N: int, n_hid: int, dir0: int, dXn, g_pooled, pool_off: int):
+    """K18c + the finish: (dW [N, H m], db [N]) of one CIN layer, over the B D rows in a fixed
+    order (per-split partials added in split order)."""
+    B, m, H, D = _cin_operands("cin_wgrad", X0, Xk, N, n_hid, dir0)
+    ld = _cin_pooled("cin_wgrad", g_pooled, "g_pooled", B, N, dir0, pool_off)
+    if dXn is not None:
+        _dev(dXn, torch.float32, "dXn")
+        if dXn.shape != (B, n_hid, D):
+            raise ValueError(f"cin_wgrad: dXn shape {tuple(dXn.shape)} != {(B, n_hid, D)}")
+    if B == 0:
+        raise ValueError("cin_wgrad: no rows")
+    dev = X0.device
+    K = H * m
+    C = lib().mirec_cin_wgrad_splits(B, m, H, D)
+    stride = lib().mirec_cin_wgrad_stride(N, K)
+    P = torch.empty(C, stride, dtype=torch.float32, device=dev)
+    with timed_launch('cin_wgrad'):
+        rc = lib().mirec_cin_wgrad_f32(ptr(X0), ptr(Xk), B, m, H, D, N, n_hid, dir0, ptr(dXn),
+                                       ptr(g_pooled), pool_off, ld, ptr(P), stream_handle())
+    check(rc, "mirec_cin_wgrad_f32")
+    if C == 1:
+        out = P[0]
+    else:
+        out = torch.empty(stride, dtype=torch.float32, device=dev)
+        check(lib().mirec_linear_grad_finish_f32(ptr(P), C, stride, ptr(out), None, 0, 0, None,
+                                                 None, None, stream_handle()),
+              "mirec_linear_grad_finish_f32")
+    nw = (N * K + 3) // 4 * 4
+    return out[:N * K].view(N, K), out[nw:nw + N]

@@ -232,6 +232,8 @@ class FusedAdam(torch.optim.Optimizer):
     # (K2) and applies the deferred step to the touched rows only; untouched rows
     # lag and are completed by flush() (window end, epoch end, state_dict()). The
     # result is bit-identical to the dense Adam the reference runs over every row.
+    DEFERRED_WIDTHS = (1, 4, 16, 32, 64, 128, 256)   # row widths the deferred K5 kernels take
+
     def enable_deferred(self, params, window: int = 256):
         """Run the deferred schedule for these 2-D parameters (width 1, 4..256)."""
         params = list(params)
@@ -248,7 +250,7 @@ class FusedAdam(torch.optim.Optimizer):
             self._sort_status = torch.zeros(ops.CHAIN_MAX_BLOCKS + 1, dtype=torch.int32,
                                             device=dev)
         for p in params:
-            if p.dim() != 2 or p.shape[1] not in (1, 4, 16, 32, 64, 128, 256) or not p.is_cuda:
+            if p.dim() != 2 or p.shape[1] not in self.DEFERRED_WIDTHS or not p.is_cuda:
                 continue
             self._ensure_state(p)
             self._deferred[p] = {'last': torch.zeros(p.shape[0], dtype=torch.int32,
