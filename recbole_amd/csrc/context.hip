@@ -649,7 +649,7 @@ extern "C" int mirec_colsum_multi_f32(const float* const* x, const int64_t* n, c
   int k = 0;
   for (int q = 0; q < n_jobs; ++q) {
     if (m[q] == 0) continue;
-    if (!x[q] || !out[q] || n[q] < 0 || m[q] < 0) {
+    if ((!x[q] && n[q] > 0) || !out[q] || n[q] < 0 || m[q] < 0) {
       set_error("mirec_colsum_multi_f32: bad job %d", q);
       return -1;
     }
@@ -727,7 +727,7 @@ extern "C" int mirec_linear_grad_finish_f32(const float* P, int32_t C, int64_t n
 
 extern "C" int mirec_colsum_f32(const float* x, int64_t n, int64_t m, float* out, void* stream) {
   if (m == 0) return 0;
-  if (!x || !out || n < 0 || m < 0) {
+  if ((!x && n > 0) || !out || n < 0 || m < 0) {   // no rows: x is never read, out = 0
     set_error("mirec_colsum_f32: bad arguments");
     return -1;
   }

@@ -43,9 +43,12 @@ def _cpu(inter):
     return {k: v.cpu() for k, v in inter.interaction.items()}
 
 
-@pytest.mark.parametrize('seq', [True, False])
-def test_loss_grads_predictions_match_oracle(tmp_path, seq):
-    config, train, valid, test, model = _pipeline(tmp_path, seq=seq)
+@pytest.mark.parametrize('seq,embedding_size',           # 10: the model's default width
+                         [(True, 16), (False, 16), (True, 10), (False, 10)],
+                         ids=['True', 'False', 'True-10', 'False-10'])
+def test_loss_grads_predictions_match_oracle(tmp_path, seq, embedding_size):
+    config, train, valid, test, model = _pipeline(tmp_path, seq=seq,
+                                                  embedding_size=embedding_size)
     ref = _oracle(model)
     b = next(iter(train)).to(config['device'])
     loss = model.calculate_loss(b)
