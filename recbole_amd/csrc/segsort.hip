@@ -4,8 +4,8 @@
 // [n_rows, d] gradient and index_adds every looked-up row into it.  Here the
 // contributions are grouped instead: a stable LSD radix sort of (row id,
 // contribution index) gives, per distinct row, the ordered list of its
-// contributions, which K5 (adam.hip) or the dense scatter below sums in that
-// fixed order — bitwise reproducible, no float atomics.
+// contributions, which K5 (adam.hip) or the dense scatter (segreduce.hip) sums in
+// that fixed order — bitwise reproducible, no float atomics.
 //
 // The sort runs in ONE workgroup (512 lanes): n is a training batch's
 // contribution count (C2: 512 user keys, 2,560 item keys), far too small to
@@ -17,6 +17,7 @@
 // take one workgroup each over global ping-pong buffers (1-bit stable splits).
 #include "common.h"
 #include "ahead.h"
+#include "lookback.h"
 
 namespace mirec {
 
@@ -225,6 +226,52 @@ struct R8Lds {
   int32_t kmin, kmax, base, last;
 };
 
+// The ballot ranking of one 64-key chunk by 8-bit digit within its wave (this kernel and
+// the onesweep passes, os_pass_kernel): the 8 digit-bit ballots intersect to the lane's
+// set of same-digit lanes m (lt: the mask of the lanes below this one). cnt[digit][wid]
+// of the [256][W waves] counters is the digit's count in the wave's earlier chunks,
+// which the digit's leader lane advances between two wave barriers; rank[i] (key i, if
+// valid) = that count + the same-digit lanes below. A fix here reaches both sorts.
+template <int W>
+__device__ __forceinline__ void rank_chunk8(uint32_t dd, bool valid, uint64_t lt, int* cnt,
+                                            int wid, uint16_t* rank, int i) {
+  uint64_t m = __ballot(valid);
+#pragma unroll
+  for (int bb = 0; bb < 8; ++bb) {             // same-digit lanes: AND of xnor(ballot, bit)
+    const int32_t sb = __builtin_amdgcn_sbfe((int32_t)dd, bb, 1);
+    const uint64_t bl = __ballot(sb != 0);
+    m &= ~(bl ^ (uint64_t)(int64_t)sb);
+  }
+  const int r = __popcll(m & lt);
+  int* h = &cnt[(int)dd * W + wid];
+  const int before = valid ? *h : 0;
+  __builtin_amdgcn_wave_barrier();
+  if (valid && r == 0) *h = before + __popcll(m);
+  __builtin_amdgcn_wave_barrier();
+  if (valid) rank[i] = (uint16_t)(before + r);
+}
+
+// Exclusive scan, digit-major, of the 256 x W counters of a block of T lanes (in place):
+// every (digit, wave) gets the offset of its keys in the block's output.
+template <int W, int T>
+__device__ __forceinline__ void scan_digit_counters(int* cnt, int* scan_lds) {
+  constexpr int per = 256 * W / T;
+  const int tid = threadIdx.x;
+  int c[per], sum = 0;
+#pragma unroll
+  for (int q = 0; q < per; ++q) {
+    c[q] = cnt[tid * per + q];
+    sum += c[q];
+  }
+  int tot;
+  int run = block_exclusive_scan(sum, scan_lds, &tot);
+#pragma unroll
+  for (int q = 0; q < per; ++q) {
+    cnt[tid * per + q] = run;
+    run += c[q];
+  }
+}
+
 #ifdef MIREC_R8_PROBE
 __device__ uint64_t g_r8_probe[16];
 #define R8T(k) do { if (threadIdx.x == 0 && blockIdx.x == 0) g_r8_probe[k] = wall_clock64(); } while (0)
@@ -312,40 +359,11 @@ __global__ __launch_bounds__(kR8Threads) void segsort_radix8_kernel(
       const int i = (wid * cpw + cc) * 64 + lane;  // one block runs cold in the I-cache)
       const bool valid = i < n;
       const uint32_t dd = valid ? ((L.k[cur][i] - kmin) >> shift) & 255u : 0u;
-      uint64_t m = __ballot(valid);
-#pragma unroll
-      for (int bb = 0; bb < 8; ++bb) {           // same-digit lanes: AND of xnor(ballot, bit)
-        const int32_t sb = __builtin_amdgcn_sbfe((int32_t)dd, bb, 1);
-        const uint64_t bl = __ballot(sb != 0);
-        const uint64_t s64 = (uint64_t)(int64_t)sb;
-        m &= ~(bl ^ s64);
-      }
-      const int r = __popcll(m & lt);
-      int* h = &L.hist[(int)dd * kR8Waves + wid];
-      const int before = valid ? *h : 0;
-      __builtin_amdgcn_wave_barrier();
-      if (valid && r == 0) *h = before + __popcll(m);
-      __builtin_amdgcn_wave_barrier();
-      if (valid) L.rank[i] = (uint16_t)(before + r);
+      rank_chunk8<kR8Waves>(dd, valid, lt, L.hist, wid, L.rank, i);
     }
     if (shift == 8) R8T(8);
     __syncthreads();
-    {                                            // exclusive scan of the counters, digit-major
-      constexpr int per = 256 * kR8Waves / kR8Threads;
-      int c[per], sum = 0;
-#pragma unroll
-      for (int q = 0; q < per; ++q) {
-        c[q] = L.hist[tid * per + q];
-        sum += c[q];
-      }
-      int tot;
-      int run = block_exclusive_scan(sum, L.scan, &tot);
-#pragma unroll
-      for (int q = 0; q < per; ++q) {
-        L.hist[tid * per + q] = run;
-        run += c[q];
-      }
-    }
+    scan_digit_counters<kR8Waves, kR8Threads>(L.hist, L.scan);
     __syncthreads();
     if (shift == 8) R8T(9);
 #pragma unroll 1
@@ -540,26 +558,6 @@ __global__ __launch_bounds__(kSortThreads) void segsort_global_kernel(
   for (int i = threadIdx.x; i < n; i += kSortThreads) perm[i] = vs[i];
   __syncthreads();
   emit_segments(ks, n, uniq, seg, n_uniq, scan_lds);
-}
-
-// Dense scatter of grouped sums (autograd-compatible path): one wave per
-// distinct row, lanes over the row's columns, contributions in fixed order.
-__global__ __launch_bounds__(256) void segment_scatter_add_kernel(
-    const float* __restrict__ rows, int d, const int32_t* __restrict__ perm,
-    const int32_t* __restrict__ uniq, const int32_t* __restrict__ seg,
-    const int32_t* __restrict__ n_uniq_dev, float* __restrict__ dense, int64_t n_rows) {
-  const int nu = n_uniq_dev[0];
-  const int lane = threadIdx.x & 63;
-  for (int u = blockIdx.x * 4 + (threadIdx.x >> 6); u < nu; u += gridDim.x * 4) {
-    const int64_t row = uniq[u];
-    if (row < 0 || row >= n_rows) continue;
-    const int s0 = seg[u], s1 = seg[u + 1];
-    for (int c = lane; c < d; c += 64) {
-      float acc = 0.f;
-      for (int i = s0; i < s1; ++i) acc += rows[(int64_t)perm[i] * d + c];
-      dense[row * d + c] += acc;
-    }
-  }
 }
 
 // ---------------------------------------------------------------------------
@@ -781,69 +779,19 @@ static int radix_segment_sort(const int64_t* keys, int n, int nbits, int32_t* pe
 // status (int32, zero before the first call, left zero: the last block of each launch
 // zeroes what that launch used): hist [kOsMaxPasses][256] | look-back words [passes]
 // [tiles][256] | segment look-back words [tiles] | tickets [kOsMaxPasses + 1]. A look-back
-// word holds 1 << 30 | the tile's own count; a tile sums its predecessors' words.
+// word holds 1 << 30 | the tile's own count; a tile sums its predecessors' words
+// (lookback.h).
 constexpr int kOsThreads = 512;
 constexpr int kOsWaves = kOsThreads / 64;
 constexpr int kOsTile = 2048;
 constexpr int kOsIpt = kOsTile / kOsThreads;       // keys per thread (loads)
 constexpr int kOsChunks = kOsTile / 64 / kOsWaves;  // 64-key chunks per wave
 constexpr int kOsMaxPasses = 4;
-constexpr uint32_t kOsFlagA = 1u << 30, kOsVal = (1u << 30) - 1;
 
 __host__ __device__ inline int64_t os_tiles(int64_t n) { return (n + kOsTile - 1) / kOsTile; }
 __host__ __device__ inline int64_t os_status_words(int64_t n) {
   const int64_t t = os_tiles(n);
   return (int64_t)kOsMaxPasses * 256 + (int64_t)kOsMaxPasses * t * 256 + t + kOsMaxPasses + 1;
-}
-
-// The look-back words carry only their own count (flag 1 << 30 | count): no data is
-// published through them, so relaxed agent-scope loads and stores suffice, and the loads
-// of many predecessors can be in flight together (an acquire load waits for itself).
-__device__ __forceinline__ uint32_t os_load(const uint32_t* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void os_store(uint32_t* p, uint32_t v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// sum of the counts of tiles h, h + H, h + 2H, ... < tile in column `words` (stride per
-// tile): every tile publishes its count before it sums, so no wait chains through
-// predecessors — 16 loads in flight per batch, a word not yet published is re-read
-__device__ __forceinline__ uint32_t os_sum_before(const uint32_t* words, int64_t tile,
-                                                  int64_t stride, int h, int H) {
-  uint32_t s = 0;
-  for (int64_t t0 = h; t0 < tile; t0 += 16 * (int64_t)H) {
-    uint32_t w[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      const int64_t t = t0 + j * (int64_t)H;
-      w[j] = t < tile ? os_load(words + t * stride) : kOsFlagA;
-    }
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      const int64_t t = t0 + j * (int64_t)H;
-      while ((w[j] >> 30) == 0) {
-        __builtin_amdgcn_s_sleep(1);
-        w[j] = os_load(words + t * stride);
-      }
-      s += t < tile ? (w[j] & kOsVal) : 0u;
-    }
-  }
-  return s;
-}
-
-// the last of the launch's blocks (ticket) zeroes `words` [0, n_words)
-__device__ __forceinline__ void os_cleanup(uint32_t* ticket, uint32_t* words, int64_t n_words,
-                                           int* flag_lds) {
-  __syncthreads();
-  if (threadIdx.x == 0)
-    *flag_lds = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ==
-                gridDim.x - 1;
-  __syncthreads();
-  if (*flag_lds) {
-    for (int64_t q = threadIdx.x; q < n_words; q += blockDim.x) words[q] = 0u;
-    if (threadIdx.x == 0) *ticket = 0u;
-  }
 }
 
 __global__ __launch_bounds__(kOsThreads) void os_hist_kernel(
@@ -916,38 +864,10 @@ __global__ __launch_bounds__(kOsThreads) void os_pass_kernel(
     const int i = (wid * kOsChunks + cc) * 64 + lane;
     const bool valid = i < tn;
     const uint32_t dd = valid ? (L.k[i] >> shift) & 255u : 0u;
-    uint64_t m = __ballot(valid);
-#pragma unroll
-    for (int bb = 0; bb < 8; ++bb) {
-      const int32_t sb = __builtin_amdgcn_sbfe((int32_t)dd, bb, 1);
-      const uint64_t bl = __ballot(sb != 0);
-      m &= ~(bl ^ (uint64_t)(int64_t)sb);
-    }
-    const int r = __popcll(m & lt);
-    int* h = &L.cnt[(int)dd * kOsWaves + wid];
-    const int before = valid ? *h : 0;
-    __builtin_amdgcn_wave_barrier();
-    if (valid && r == 0) *h = before + __popcll(m);
-    __builtin_amdgcn_wave_barrier();
-    if (valid) L.rank[i] = (uint16_t)(before + r);
+    rank_chunk8<kOsWaves>(dd, valid, lt, L.cnt, wid, L.rank, i);
   }
   __syncthreads();
-  {                                              // digit-major offsets inside the tile
-    constexpr int per = 256 * kOsWaves / kOsThreads;
-    int c[per], sum = 0;
-#pragma unroll
-    for (int q = 0; q < per; ++q) {
-      c[q] = L.cnt[tid * per + q];
-      sum += c[q];
-    }
-    int tot;
-    int run = block_exclusive_scan(sum, L.scan, &tot);
-#pragma unroll
-    for (int q = 0; q < per; ++q) {
-      L.cnt[tid * per + q] = run;
-      run += c[q];
-    }
-  }
+  scan_digit_counters<kOsWaves, kOsThreads>(L.cnt, L.scan);   // offsets inside the tile
   __syncthreads();
   if (tid < 256) L.tstart[tid] = L.cnt[tid * kOsWaves];
   if (tid == 0) L.tstart[256] = tn;
@@ -1031,585 +951,6 @@ __global__ __launch_bounds__(kOsThreads) void os_seg_kernel(
   os_cleanup(ticket, look, tiles, &last);
 }
 
-// ---------------------------------------------------------------------------
-// Chunked segmented scatter-add (hot rows: a Zipf head row may own 10^4..10^5
-// contributions, far too many for one wave to sum serially). Every segment is cut
-// into pieces of CH = scat_chunk(d) positions counted from ITS OWN start, so a row's
-// sum depends only on its own contributions and their order — not on where the row
-// sits in the sorted array (a row-sharded owner's shorter array gives the one-process
-// sums bit for bit). Work is dealt by absolute chunks of CH positions: the group of G
-// lanes of chunk c sums every piece that STARTS in c (reading past c's end when the
-// piece does) — the pieces of the segments that start in c, plus at most one later
-// piece of the segment that started before c. A one-piece segment is written
-// directly; a longer one leaves its first piece in tail[chunk of its start] and
-// piece k in head[that chunk + k] (at most one of each per chunk), which the fixup
-// kernel (owner: the block of the first boundary after the segment's start) adds in
-// piece order. Deterministic, no float atomics.
-// positions per chunk: short chunks for wide rows (more lane groups in flight),
-// longer ones for narrow rows; the workspace is sized for the smallest
-#ifndef MIREC_SCAT_NARROW_CH
-#define MIREC_SCAT_NARROW_CH 8
-#endif
-// 8 positions per piece up to d = 16 (DeepFM tokens: C4 4.34 -> 4.54 M samples/s against 32)
-__host__ __device__ __forceinline__ int scat_chunk(int d) {
-  return d == 1 ? 8 : d <= 16 ? MIREC_SCAT_NARROW_CH : 32;
-}
-constexpr int kScatChunkMin = 8;
-
-__device__ __forceinline__ int seg_of(const int32_t* __restrict__ seg, int nu, int p) {
-  int lo = 0, hi = nu - 1;   // largest u with seg[u] <= p
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (seg[mid] <= p) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
-// PAIR (mirec_segment_reduce2_f32): a second, one-column source grouped by the same
-// segments (DeepFM's first-order [V, 1] weights beside the [V, d] token rows) is summed
-// by lane 0 of each group in the same pass, position by position in the same order as
-// the one-column kernel; its pieces go to head1 / tail1.
-template <int G, int DMAX, bool PAIR = false>
-__global__ __launch_bounds__(256) void scatter_chunks_kernel(
-    const float* __restrict__ rows, int d, const int32_t* __restrict__ perm,
-    const int32_t* __restrict__ uniq, const int32_t* __restrict__ seg,
-    const int32_t* __restrict__ n_uniq_dev, float* __restrict__ dense, int64_t n_rows,
-    float* __restrict__ head, float* __restrict__ tail, int32_t* __restrict__ tail_seg,
-    int n_chunks, int compact, const float* __restrict__ rows1 = nullptr,
-    float* __restrict__ dense1 = nullptr, float* __restrict__ head1 = nullptr,
-    float* __restrict__ tail1 = nullptr) {
-  const int nu = n_uniq_dev[0];
-  const int n = seg[nu];
-  const int lane = threadIdx.x & 63;
-  const int gi = lane / G, l = lane % G;
-  const int c = (int)(((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / 64) * (64 / G) + gi;
-  if (c >= n_chunks) return;
-  const int CH = scat_chunk(d);
-  const int p0 = c * CH;
-  if (nu == 0 || p0 >= n) {
-    if (l == 0) tail_seg[c] = -1;
-    return;
-  }
-  const int p1 = min(n, p0 + CH);
-  constexpr int MAXC = DMAX / G;    // columns per lane, d <= DMAX
-  // sums positions [q0, q1) of one segment into acc (loads 4 positions ahead of the adds)
-  float acc1 = 0.f;                         // PAIR: the one-column source (lane 0)
-  auto piece = [&](int q0, int q1, float* acc) {
-    int q = q0;
-#pragma unroll
-    for (int j = 0; j < MAXC; ++j) acc[j] = 0.f;
-    acc1 = 0.f;
-    for (; q + 4 <= q1; q += 4) {
-      int pr[4];
-#pragma unroll
-      for (int t = 0; t < 4; ++t) pr[t] = perm[q + t];
-      float v[4][MAXC];
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int j = 0; j < MAXC; ++j) {
-          const int col = l + j * G;
-          v[t][j] = col < d ? rows[(int64_t)pr[t] * d + col] : 0.f;
-        }
-      float v1[4];
-      if (PAIR) {
-#pragma unroll
-        for (int t = 0; t < 4; ++t) v1[t] = l == 0 ? rows1[pr[t]] : 0.f;
-      }
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int j = 0; j < MAXC; ++j) acc[j] += v[t][j];
-      if (PAIR) {
-#pragma unroll
-        for (int t = 0; t < 4; ++t) acc1 += v1[t];
-      }
-    }
-    for (; q < q1; ++q) {
-      const float* r = rows + (int64_t)perm[q] * d;
-#pragma unroll
-      for (int j = 0; j < MAXC; ++j) {
-        const int col = l + j * G;
-        if (col < d) acc[j] += r[col];
-      }
-      if (PAIR && l == 0) acc1 += rows1[perm[q]];
-    }
-  };
-  auto store1 = [&](float* dst) {
-    if (PAIR && l == 0 && dst) *dst = acc1;
-  };
-  auto store = [&](float* dst, const float* acc, bool add) {
-#pragma unroll
-    for (int j = 0; j < MAXC; ++j) {
-      const int col = l + j * G;
-      if (dst && col < d) {
-        if (add) dst[col] += acc[j]; else dst[col] = acc[j];
-      }
-    }
-  };
-  float acc[MAXC];
-  int u = seg_of(seg, nu, p0);
-  if (seg[u] < p0) {                       // the segment that started before this chunk
-    const int s0 = seg[u], e = seg[u + 1];
-    const int ps = s0 + (p0 - s0 + CH - 1) / CH * CH;   // its next piece start >= p0
-    if (ps < p1 && ps < e) {
-      piece(ps, min(e, ps + CH), acc);
-      store(head + (int64_t)c * d, acc, false);
-      store1(PAIR ? head1 + c : nullptr);
-    }
-    ++u;
-  }
-  int ts = -1;                              // the multi-piece segment starting here, if any
-  for (; u < nu && seg[u] < p1; ++u) {     // the segments that start in this chunk
-    const int s0 = seg[u], e = seg[u + 1];
-    piece(s0, min(e, s0 + CH), acc);
-    if (e - s0 <= CH) {
-      const int64_t row = compact ? (int64_t)u : (int64_t)uniq[u];
-      store((row >= 0 && row < n_rows) ? dense + row * d : nullptr, acc, !compact);
-      store1(PAIR ? dense1 + u : nullptr);       // PAIR: compact outputs only
-    } else {
-      store(tail + (int64_t)c * d, acc, false);
-      store1(PAIR ? tail1 + c : nullptr);
-      ts = u;
-    }
-  }
-  if (l == 0) tail_seg[c] = ts;            // the fixup's owner list: no search there
-}
-
-// Fixup of the multi-piece segments: the owner of boundary b is the segment that starts
-// in chunk b - 1 and continues (tail_seg, written by the chunk kernel). Its sum is
-// defined by 256 partial sums per column block of CW = d rounded up to a power of two
-// columns: "thread" i (column cb + i % CW, kl = i / CW, KL = 256 / CW) sums
-// [tail[b-1] if kl = 0] + head[b + kl] + head[b + kl + KL] + ..., and the column's sum
-// is t = s_0 + s_1 + ... + s_{KL-1} in kl order — deterministic. One wave per boundary
-// forms the 256 partial sums (four per lane, their loads in flight together), stages
-// them in its LDS slice and folds them; four boundaries per workgroup. The one-column
-// source of a pair uses the same rule with CW = 1 (KL = 256).
-constexpr int kFixWaves = 4;
-__global__ __launch_bounds__(64 * kFixWaves) void scatter_fixup_kernel(
-    int d, const int32_t* __restrict__ uniq, const int32_t* __restrict__ seg,
-    const int32_t* __restrict__ tail_seg, float* __restrict__ dense, int64_t n_rows,
-    const float* __restrict__ head, const float* __restrict__ tail, int n_chunks, int compact,
-    float* __restrict__ dense1 = nullptr, const float* __restrict__ head1 = nullptr,
-    const float* __restrict__ tail1 = nullptr) {
-  __shared__ float red[kFixWaves][256];
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int b = 1 + (int)blockIdx.x * kFixWaves + w;           // this wave's boundary
-  if (b >= n_chunks) return;
-  const int u = tail_seg[b - 1];
-  if (u < 0) return;
-  const int CH = scat_chunk(d);
-  const int s0 = seg[u], e = seg[u + 1];
-  const int kend = b - 2 + (e - s0 + CH - 1) / CH;     // chunk holding its last piece's start
-  const int64_t row = compact ? (int64_t)u : (int64_t)uniq[u];
-  if (row < 0 || row >= n_rows) return;
-  float* R = red[w];
-  // partial sums of "threads" i = lane + 64 j over src (ld columns, CW, KL), into R
-  auto partials = [&](const float* __restrict__ hs, const float* __restrict__ ts, int ld, int cb,
-                      int CW, int KL) {
-    float acc[4];
-    int col[4], kl[4];
-    // loads are unconditional (clamped to a valid address) and the term is selected
-    // afterwards: loads under per-lane branches wait for each other
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int i = lane + 64 * j;
-      col[j] = cb + i % CW;
-      kl[j] = i / CW;
-      const float tv = ts[(int64_t)(b - 1) * ld + min(col[j], ld - 1)];
-      acc[j] = (kl[j] == 0 && col[j] < ld) ? tv : 0.f;
-    }
-    for (int r0 = 0; b + r0 * KL <= kend; r0 += 4) {   // four rounds' loads in flight
-      float hv[4][4];
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int k = min(b + kl[j] + (r0 + rr) * KL, kend);
-          hv[rr][j] = hs[(int64_t)k * ld + min(col[j], ld - 1)];
-        }
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if (col[j] < ld && b + kl[j] + (r0 + rr) * KL <= kend) acc[j] += hv[rr][j];
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) R[lane + 64 * j] = acc[j];
-  };
-  int cw = 1;
-  while (cw < d && cw < 256) cw <<= 1;
-  const int KL = 256 / cw;
-  for (int cb = 0; cb < d; cb += cw) {
-    partials(head, tail, d, cb, cw, KL);
-    __builtin_amdgcn_wave_barrier();                // one wave: its LDS ops stay in order
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int i = lane + 64 * j;
-      if (i < cw && cb + i < d) {
-        float t = R[i];
-        for (int z = 1; z < KL; ++z) t += R[z * cw + i];
-        if (compact) dense[row * d + cb + i] = t; else dense[row * d + cb + i] += t;
-      }
-    }
-    __builtin_amdgcn_wave_barrier();
-  }
-  if (dense1) {          // PAIR: the one-column source, as the d = 1 fixup sums it
-    partials(head1, tail1, 1, 0, 1, 256);
-    __builtin_amdgcn_wave_barrier();
-    if (lane == 0) {
-      // partial sums without a term are +0: adding them in order only turns a -0 running
-      // sum into +0, which one add of +0 does as well
-      const int m = min(256, kend - b + 1);
-      float t = R[0];
-      for (int z = 1; z < m; ++z) t += R[z];
-      if (m < 256) t += 0.f;
-      dense1[row] = t;
-    }
-  }
-}
-
-static inline unsigned fixup_blocks(int n_chunks) {
-  return (unsigned)((n_chunks - 1 + kFixWaves - 1) / kFixWaves);
-}
-
-// Narrow rows (2 <= d <= 16) with pos_seg (the segment of every sorted position, from
-// the chained block sort): chunk c of CH = 8 sorted positions owns the same pieces as
-// in scatter_chunks_kernel (pieces counted from each segment's first position) — those
-// whose start lies in [p0, p1) — and sums them in the same order, so the outputs are
-// bit for bit the same. No search and no serial walk over segments: the 16 lanes of a
-// group each resolve one position of the window [p0, p0 + 2 CH) (its perm, segment,
-// piece, whether the chunk owns it, piece start / end), every lane then loads its
-// column of the 16 window rows at once and folds them in order.
-constexpr int kWinKindFinal = 0, kWinKindTail = 1, kWinKindHead = 2;
-template <bool PAIR>
-__global__ __launch_bounds__(256) void scatter_window_kernel(
-    const float* __restrict__ rows, int d, const int32_t* __restrict__ perm,
-    const int32_t* __restrict__ pos_seg, const int32_t* __restrict__ uniq,
-    const int32_t* __restrict__ seg, const int32_t* __restrict__ n_uniq_dev,
-    float* __restrict__ dense, int64_t n_rows, float* __restrict__ head,
-    float* __restrict__ tail, int32_t* __restrict__ tail_seg, int n_chunks, int compact,
-    const float* __restrict__ rows1, float* __restrict__ dense1, float* __restrict__ head1,
-    float* __restrict__ tail1) {
-  constexpr int G = 16, CH = 8, W = 2 * CH;
-  const int nu = n_uniq_dev[0];
-  const int n = seg[nu];
-  const int lane = threadIdx.x & 63, gb = lane & ~(G - 1), l = lane & (G - 1);
-  const int c = (int)(((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / G);
-  if (c >= n_chunks) return;
-  const int p0 = c * CH;
-  if (nu == 0 || p0 >= n) {
-    if (l == 0) tail_seg[c] = -1;
-    return;
-  }
-  const int p1 = min(n, p0 + CH);
-  // lane l resolves window position q = p0 + l
-  const int q = p0 + l;
-  int pq = 0, info = 0, dst = 0;      // info: 1 owned | 2 piece start | 4 piece end | kind << 3
-  if (q < n) {
-    pq = perm[q];
-    const int u = pos_seg[q];
-    const int s0 = seg[u], e = seg[u + 1];
-    const int ps = s0 + (q - s0) / CH * CH;
-    if (ps >= p0 && ps < p1) {
-      const int pe = min(e, ps + CH);
-      const int kind = ps != s0 ? kWinKindHead : (e - s0 <= CH ? kWinKindFinal : kWinKindTail);
-      info = 1 | (q == ps ? 2 : 0) | (q == pe - 1 ? 4 : 0) | (kind << 3);
-      dst = kind == kWinKindFinal ? (compact ? u : uniq[u]) : u;
-    }
-  }
-  // the multi-piece segment starting here (its first piece is a tail piece), if any
-  const uint64_t tb = __ballot((info & 2) && (info >> 3) == kWinKindTail);
-  const uint64_t gm = tb & (0xFFFFull << gb);
-  const int tl = gm ? __builtin_ctzll(gm) : gb;
-  const int tsu = __shfl(dst, tl, 64);
-  if (l == 0) tail_seg[c] = gm ? tsu : -1;
-  int pt[W], it[W], dt[W];
-#pragma unroll
-  for (int t = 0; t < W; ++t) {
-    pt[t] = __shfl(pq, gb + t, 64);
-    it[t] = __shfl(info, gb + t, 64);
-    dt[t] = __shfl(dst, gb + t, 64);
-  }
-  // every lane loads all W rows (unowned positions read row pt = 0 of a valid position;
-  // their terms are skipped below): loads under per-lane branches wait for each other
-  float v[W], v1[W];
-  const int lc = min(l, d - 1);
-#pragma unroll
-  for (int t = 0; t < W; ++t) {
-    v[t] = rows[(int64_t)pt[t] * d + lc];
-    if (PAIR) v1[t] = rows1[pt[t]];
-  }
-  float acc = 0.f, acc1 = 0.f;
-#pragma unroll
-  for (int t = 0; t < W; ++t) {
-    if (!(it[t] & 1)) continue;
-    acc = ((it[t] & 2) ? 0.f : acc) + v[t];
-    if (PAIR) acc1 = ((it[t] & 2) ? 0.f : acc1) + v1[t];
-    if (!(it[t] & 4)) continue;
-    const int kind = it[t] >> 3;
-    if (kind == kWinKindFinal) {
-      const int64_t row = dt[t];
-      if (l < d && row >= 0 && row < n_rows) {
-        if (compact) dense[row * d + l] = acc; else dense[row * d + l] += acc;
-      }
-      if (PAIR && l == 0) dense1[dt[t]] = acc1;
-    } else {
-      float* out = (kind == kWinKindTail ? tail : head) + (int64_t)c * d;
-      if (l < d) out[l] = acc;
-      if (PAIR && l == 0) (kind == kWinKindTail ? tail1 : head1)[c] = acc1;
-    }
-  }
-}
-
-// Wide rows (16 < d <= 256) with pos_seg: chunk c of CH = 32 sorted positions owns the
-// same pieces as scatter_chunks_kernel and sums them in the same order (bit for bit).
-// One wave per chunk: lane l resolves window position p0 + l of [p0, p0 + 64) (perm,
-// segment, piece, ownership); then the wave walks the window in order, eight positions'
-// row loads in flight at a time — position t's perm and flags come from lane t by
-// readlane, so the walk is uniform (scalar branches) and every row read is one coalesced
-// access of the lanes' columns (l, l + 64, ...).
-template <int MAXC>
-__global__ __launch_bounds__(256) void scatter_wide_window_kernel(
-    const float* __restrict__ rows, int d, const int32_t* __restrict__ perm,
-    const int32_t* __restrict__ pos_seg, const int32_t* __restrict__ uniq,
-    const int32_t* __restrict__ seg, const int32_t* __restrict__ n_uniq_dev,
-    float* __restrict__ dense, int64_t n_rows, float* __restrict__ head,
-    float* __restrict__ tail, int32_t* __restrict__ tail_seg, int n_chunks, int compact) {
-  constexpr int CH = 32, W = 64;
-  const int nu = n_uniq_dev[0];
-  const int n = seg[nu];
-  const int lane = threadIdx.x & 63;
-  const int c = __builtin_amdgcn_readfirstlane(
-      (int)(((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6));
-  if (c >= n_chunks) return;
-  const int p0 = c * CH;
-  if (nu == 0 || p0 >= n) {
-    if (lane == 0) tail_seg[c] = -1;
-    return;
-  }
-  const int p1 = min(n, p0 + CH);
-  const int q = p0 + lane;
-  int pq = 0, info = 0, dst = 0;      // info: 1 owned | 2 piece start | 4 piece end | kind << 3
-  if (q < n) {
-    pq = perm[q];
-    const int u = pos_seg[q];
-    const int s0 = seg[u], e = seg[u + 1];
-    const int ps = s0 + (q - s0) / CH * CH;
-    if (ps >= p0 && ps < p1) {
-      const int pe = min(e, ps + CH);
-      const int kind = ps != s0 ? kWinKindHead : (e - s0 <= CH ? kWinKindFinal : kWinKindTail);
-      info = 1 | (q == ps ? 2 : 0) | (q == pe - 1 ? 4 : 0) | (kind << 3);
-      dst = kind == kWinKindFinal ? (compact ? u : uniq[u]) : u;
-    }
-  }
-  const uint64_t tb = __ballot((info & 2) && (info >> 3) == kWinKindTail);
-  const int tsu = tb ? __builtin_amdgcn_readlane(dst, __builtin_ctzll(tb)) : -1;
-  if (lane == 0) tail_seg[c] = tsu;
-  int col[MAXC];
-#pragma unroll
-  for (int j = 0; j < MAXC; ++j) col[j] = min(lane + 64 * j, d - 1);
-  float acc[MAXC];
-#pragma unroll
-  for (int j = 0; j < MAXC; ++j) acc[j] = 0.f;
-  for (int t0 = 0; t0 < W; t0 += 8) {
-    int it[8], pt[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      it[j] = __builtin_amdgcn_readlane(info, t0 + j);
-      pt[j] = __builtin_amdgcn_readlane(pq, t0 + j);
-    }
-    float v[8][MAXC];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-#pragma unroll
-      for (int cc = 0; cc < MAXC; ++cc)
-        v[j][cc] = (it[j] & 1) ? rows[(int64_t)pt[j] * d + col[cc]] : 0.f;
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      if (!(it[j] & 1)) continue;
-#pragma unroll
-      for (int cc = 0; cc < MAXC; ++cc) acc[cc] = ((it[j] & 2) ? 0.f : acc[cc]) + v[j][cc];
-      if (!(it[j] & 4)) continue;
-      const int kind = it[j] >> 3;
-      const int dt = __builtin_amdgcn_readlane(dst, t0 + j);
-      if (kind == kWinKindFinal) {
-        const int64_t row = dt;
-        if (row >= 0 && row < n_rows) {
-#pragma unroll
-          for (int cc = 0; cc < MAXC; ++cc) {
-            const int cl = lane + 64 * cc;
-            if (cl < d) {
-              if (compact) dense[row * d + cl] = acc[cc]; else dense[row * d + cl] += acc[cc];
-            }
-          }
-        }
-      } else {
-        float* out = (kind == kWinKindTail ? tail : head) + (int64_t)c * d;
-#pragma unroll
-        for (int cc = 0; cc < MAXC; ++cc) {
-          const int cl = lane + 64 * cc;
-          if (cl < d) out[cl] = acc[cc];
-        }
-      }
-    }
-  }
-}
-
-// Union of two reduced gradients (the deferred optimizer's second level, one table read
-// by two autograd Functions): A = (uA[0..nA), rowsA), B = (uB[0..nB), rowsB), each
-// ascending and distinct. Output: the union rows ascending, each row's sum formed as the
-// second-level segment_reduce of [A's rows; B's rows] formed it — (0 + a) + b, 0 + a,
-// 0 + b — where a_pre = 1 takes a as already carrying its leading 0 + (a previous
-// merge's output): the same bits, with no sort of the concatenated keys and no reduce.
-// Two launches: a stable merge of the key lists (A before B on equal keys) into the
-// merged order, then the run heads (tile counts summed over the tiles before, as in
-// os_seg_kernel) with each head's one or two rows summed by a wave.
-__device__ __forceinline__ int merge_lower(const int32_t* __restrict__ a, int n, int32_t key) {
-  int lo = 0, hi = n;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (a[mid] < key) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-__device__ __forceinline__ int merge_upper(const int32_t* __restrict__ a, int n, int32_t key) {
-  int lo = 0, hi = n;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (a[mid] <= key) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-
-__global__ __launch_bounds__(256) void merge_place_kernel(
-    const int32_t* __restrict__ uA, const int32_t* __restrict__ nA_dev, int capA,
-    const int32_t* __restrict__ uB, const int32_t* __restrict__ nB_dev, int capB,
-    int32_t* __restrict__ mk, int32_t* __restrict__ ref) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int nA = nA_dev[0], nB = nB_dev[0];
-  if (i < capA) {
-    if (i >= nA) return;
-    const int32_t key = uA[i];
-    const int pos = (int)i + merge_lower(uB, nB, key);
-    mk[pos] = key;
-    ref[pos] = (int32_t)i;
-  } else if (i < (int64_t)capA + capB) {
-    const int j = (int)(i - capA);
-    if (j >= nB) return;
-    const int32_t key = uB[j];
-    const int pos = j + merge_upper(uA, nA, key);
-    mk[pos] = key;
-    ref[pos] = (int32_t)(0x80000000u | (uint32_t)j);
-  }
-}
-
-constexpr int kMergeThreads = 256;
-constexpr int kMergeIpt = 2;
-constexpr int kMergeTile = kMergeThreads * kMergeIpt;   // merged positions per workgroup
-
-// one output row's (up to two) source rows folded, V floats at column c
-template <int V>
-__device__ __forceinline__ void merge_fold(const float* __restrict__ s0,
-                                           const float* __restrict__ s1, bool pre0, bool two,
-                                           float* __restrict__ dst) {
-#pragma unroll
-  for (int e = 0; e < V; ++e) {
-    float v = s0[e];
-    if (!pre0) v = 0.f + v;
-    if (two) v = v + s1[e];
-    dst[e] = v;
-  }
-}
-
-template <int V>
-__global__ __launch_bounds__(kMergeThreads) void merge_compact_kernel(
-    const int32_t* __restrict__ mk, const int32_t* __restrict__ ref,
-    const int32_t* __restrict__ nA_dev, const int32_t* __restrict__ nB_dev,
-    const float* __restrict__ rowsA, const float* __restrict__ rowsB, int d, int a_pre,
-    int32_t* __restrict__ uniq_out, int32_t* __restrict__ n_out, float* __restrict__ rows_out,
-    uint32_t* __restrict__ look, uint32_t* __restrict__ ticket) {
-  __shared__ int scan[kMergeThreads / 64 + 1];
-  __shared__ int hp[kMergeTile];                  // merged position of each run head
-  __shared__ int h0[kMergeTile], h1[kMergeTile];  // each head's source rows
-  __shared__ int prefix, n_heads, last;
-  const int m = nA_dev[0] + nB_dev[0];
-  const int64_t tile = blockIdx.x;
-  const int base = (int)(tile * kMergeTile);
-  const int i0 = base + threadIdx.x * kMergeIpt;
-  int f = 0;
-#pragma unroll
-  for (int j = 0; j < kMergeIpt; ++j) {
-    const int p = i0 + j;
-    if (p < m) f += (p == 0 || mk[p - 1] != mk[p]) ? 1 : 0;
-  }
-  int tot;
-  const int ex = block_exclusive_scan(f, scan, &tot);
-  if (threadIdx.x == 0) os_store(look + tile, kOsFlagA | (uint32_t)tot);
-  {
-    const uint32_t part = os_sum_before(look, tile, 1, threadIdx.x, kMergeThreads);
-    int all;
-    (void)block_exclusive_scan((int)part, scan, &all);
-    if (threadIdx.x == 0) {
-      prefix = all;
-      n_heads = tot;
-      if (tile == gridDim.x - 1) n_out[0] = all + tot;
-    }
-  }
-  int o = ex;
-#pragma unroll
-  for (int j = 0; j < kMergeIpt; ++j) {
-    const int p = i0 + j;
-    if (p < m && (p == 0 || mk[p - 1] != mk[p])) hp[o++] = p;
-  }
-  __syncthreads();
-  // per head: its one or two source rows, resolved once (LDS), uniq written
-  for (int h = threadIdx.x; h < n_heads; h += kMergeThreads) {
-    const int p = hp[h];
-    const int32_t key = mk[p];
-    const int r0 = ref[p];
-    const bool two = p + 1 < m && mk[p + 1] == key;
-    h0[h] = r0;                                    // A row, or B row | 0x80000000
-    h1[h] = two ? (ref[p + 1] & 0x7fffffff) : -1;  // the B row of a row in both
-    uniq_out[prefix + h] = key;
-  }
-  __syncthreads();
-  // (head, column group) items over the block's lanes, eight items' loads in flight
-  const int dv = d / V;
-  const int items = n_heads * dv;
-  for (int it0 = threadIdx.x; it0 < items; it0 += 8 * kMergeThreads) {
-    float a[8][V], b[8][V];
-    int hh[8], cc[8];
-    bool tw[8], pre[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int it = min(it0 + j * kMergeThreads, items - 1);
-      const int h = it / dv;
-      cc[j] = (it - h * dv) * V;
-      hh[j] = h;
-      const int r0 = h0[h], r1 = h1[h];
-      tw[j] = r1 >= 0;
-      const bool fromA = r0 >= 0;
-      pre[j] = fromA && a_pre;
-      const float* s0 = (fromA ? rowsA + (int64_t)r0 * d
-                               : rowsB + (int64_t)(r0 & 0x7fffffff) * d) + cc[j];
-      const float* s1 = rowsB + (int64_t)(tw[j] ? r1 : 0) * d + cc[j];
-#pragma unroll
-      for (int e = 0; e < V; ++e) {
-        a[j][e] = s0[e];
-        b[j][e] = s1[e];
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      if (it0 + j * kMergeThreads >= items) continue;
-      merge_fold<V>(a[j], b[j], pre[j], tw[j], rows_out + (int64_t)(prefix + hh[j]) * d + cc[j]);
-    }
-  }
-  os_cleanup(ticket, look, gridDim.x, &last);
-}
-
 }  // namespace mirec
 
 using namespace mirec;
@@ -1630,8 +971,7 @@ extern "C" int mirec_segment_sort_batched(const int64_t* keys, int64_t n, int64_
     return -1;
   }
   hipStream_t st = (hipStream_t)stream;
-  int nb = 0;
-  while (nb < 31 && ((int64_t)1 << nb) < key_space) ++nb;
+  const int nb = nbits_for(key_space);
   if (n == 0) {  // one empty batch: seg[0] = 0, n_uniq = 0
     hipLaunchKernelGGL(segsort_lds_kernel, dim3(1), dim3(kSortThreads), 0, st, keys, (int64_t)0,
                        1, nb, perm, uniq, seg, n_uniq_dev);
@@ -1685,8 +1025,7 @@ extern "C" int mirec_segment_sort_blocks(const int64_t* keys, int64_t n, int64_t
   int32_t* uniq_t = perm_t + nb * block_n;
   int32_t* seg_t = uniq_t + nb * block_n;
   int32_t* nu_t = seg_t + nb * (block_n + 1);
-  int nbits = 0;
-  while (nbits < 31 && ((int64_t)1 << nbits) < key_space) ++nbits;
+  const int nbits = nbits_for(key_space);
   hipStream_t st = (hipStream_t)stream;
   if (block_n <= kR8Max)       // 8-bit digits over the block's key span
     hipLaunchKernelGGL(segsort_radix8_kernel, dim3((unsigned)nb), dim3(kR8Threads), 0, st, keys,
@@ -1773,8 +1112,7 @@ extern "C" int mirec_segment_sort_onesweep(const int64_t* keys, int64_t n, int64
               (long long)os_status_words(n));
     return -1;
   }
-  int nbits = 0;
-  while (nbits < 31 && ((int64_t)1 << nbits) < key_space) ++nbits;
+  const int nbits = nbits_for(key_space);
   const int passes = nbits == 0 ? 1 : (nbits + 7) / 8;
   const int64_t tiles = os_tiles(n);
   uint32_t* hist = (uint32_t*)status;
@@ -1806,210 +1144,6 @@ extern "C" int mirec_segment_sort(const int64_t* keys, int64_t n, int64_t key_sp
                                   int32_t* n_uniq_dev, void* ws, size_t ws_bytes, void* stream) {
   return mirec_segment_sort_batched(keys, n, n > 0 ? n : 1, key_space, perm, uniq, seg,
                                     n_uniq_dev, ws, ws_bytes, stream);
-}
-
-extern "C" size_t mirec_segment_scatter_add_workspace_size(int64_t n, int32_t d) {
-  const int64_t chunks = (n + kScatChunkMin - 1) / kScatChunkMin;
-  return (size_t)2 * (size_t)chunks * (size_t)(d > 0 ? d : 1) * sizeof(float) +
-         (size_t)chunks * sizeof(int32_t) + 256;
-}
-
-static int scatter_impl(const float* rows, int32_t d, const int32_t* perm, const int32_t* uniq,
-                        const int32_t* seg, const int32_t* n_uniq_dev, int64_t n, float* dense,
-                        int64_t n_rows, void* ws, size_t ws_bytes, int compact, void* stream) {
-  if (n == 0) return 0;
-  if (!rows || !perm || !uniq || !seg || !n_uniq_dev || !dense || d <= 0 || d > 256 || n < 0 ||
-      n > INT32_MAX) {
-    set_error("mirec_segment_scatter_add_f32: bad arguments (1 <= d <= 256)");
-    return -1;
-  }
-  if (!ws || ws_bytes < mirec_segment_scatter_add_workspace_size(n, d)) {
-    set_error("mirec_segment_scatter_add_f32: workspace too small");
-    return -1;
-  }
-  const int chunks = (int)((n + scat_chunk(d) - 1) / scat_chunk(d));
-  float* head = (float*)ws;
-  float* tail = head + (int64_t)chunks * d;
-  int32_t* tail_seg = (int32_t*)(tail + (int64_t)chunks * d);
-  hipStream_t st = (hipStream_t)stream;
-#define MIREC_SCAT(GG, DM)                                                                    \
-  {                                                                                          \
-    const int64_t groups_per_block = 4 * (64 / GG);                                          \
-    hipLaunchKernelGGL((scatter_chunks_kernel<GG, DM>),                                       \
-                       dim3((unsigned)((chunks + groups_per_block - 1) / groups_per_block)),  \
-                       dim3(256), 0, st, rows, d, perm, uniq, seg, n_uniq_dev, dense, n_rows, \
-                       head, tail, tail_seg, chunks, compact);                                \
-  }
-  if (d == 1) MIREC_SCAT(1, 1)
-  else if (d <= 4) MIREC_SCAT(4, 4)
-  else if (d <= 16) MIREC_SCAT(16, 16)
-  else if (d <= 32) MIREC_SCAT(32, 32)
-  else if (d <= 64) MIREC_SCAT(64, 64)
-  else MIREC_SCAT(64, 256)
-#undef MIREC_SCAT
-  if (chunks > 1)
-    hipLaunchKernelGGL(scatter_fixup_kernel, dim3(fixup_blocks(chunks)), dim3(64 * kFixWaves), 0,
-                       st, d,
-                       uniq, seg, tail_seg, dense, n_rows, head, tail, chunks, compact);
-  return launch_status("mirec_segment_scatter_add_f32");
-}
-
-extern "C" int mirec_segment_scatter_add_f32(const float* rows, int32_t d, const int32_t* perm,
-                                             const int32_t* uniq, const int32_t* seg,
-                                             const int32_t* n_uniq_dev, int64_t n, float* dense,
-                                             int64_t n_rows, void* ws, size_t ws_bytes,
-                                             void* stream) {
-  return scatter_impl(rows, d, perm, uniq, seg, n_uniq_dev, n, dense, n_rows, ws, ws_bytes, 0,
-                      stream);
-}
-
-static int reduce2_impl(const float* rows, int32_t d, const float* rows1, const int32_t* perm,
-                        const int32_t* pos_seg, const int32_t* uniq, const int32_t* seg,
-                        const int32_t* n_uniq_dev, int64_t n, float* out, float* out1, void* ws,
-                        size_t ws_bytes, void* stream) {
-  if (n == 0) return 0;
-  if (!rows || !rows1 || !perm || !uniq || !seg || !n_uniq_dev || !out || !out1 || d < 2 ||
-      d > 16 || n < 0 || n > INT32_MAX) {
-    set_error("mirec_segment_reduce2_f32: bad arguments (2 <= d <= 16)");
-    return -1;
-  }
-  if (!ws || ws_bytes < mirec_segment_scatter_add_workspace_size(n, d + 1)) {
-    set_error("mirec_segment_reduce2_f32: workspace too small");
-    return -1;
-  }
-  static_assert(MIREC_SCAT_NARROW_CH == 8, "the pair needs the one-column chunk size");
-  const int chunks = (int)((n + scat_chunk(d) - 1) / scat_chunk(d));
-  float* head = (float*)ws;
-  float* tail = head + (int64_t)chunks * d;
-  float* head1 = tail + (int64_t)chunks * d;
-  float* tail1 = head1 + chunks;
-  int32_t* tail_seg = (int32_t*)(tail1 + chunks);
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t gpb = 4 * (64 / 16);
-  if (pos_seg)
-    hipLaunchKernelGGL((scatter_window_kernel<true>), dim3((unsigned)((chunks + gpb - 1) / gpb)),
-                       dim3(256), 0, st, rows, d, perm, pos_seg, uniq, seg, n_uniq_dev, out, n,
-                       head, tail, tail_seg, chunks, 1, rows1, out1, head1, tail1);
-  else if (d <= 4)
-    hipLaunchKernelGGL((scatter_chunks_kernel<4, 4, true>),
-                       dim3((unsigned)((chunks + 4 * 16 - 1) / (4 * 16))), dim3(256), 0, st, rows,
-                       d, perm, uniq, seg, n_uniq_dev, out, n, head, tail, tail_seg, chunks, 1,
-                       rows1, out1, head1, tail1);
-  else
-    hipLaunchKernelGGL((scatter_chunks_kernel<16, 16, true>),
-                       dim3((unsigned)((chunks + gpb - 1) / gpb)), dim3(256), 0, st, rows, d,
-                       perm, uniq, seg, n_uniq_dev, out, n, head, tail, tail_seg, chunks, 1,
-                       rows1, out1, head1, tail1);
-  if (chunks > 1)
-    hipLaunchKernelGGL(scatter_fixup_kernel, dim3(fixup_blocks(chunks)), dim3(64 * kFixWaves), 0,
-                       st, d,
-                       uniq, seg, tail_seg, out, n, head, tail, chunks, 1, out1, head1, tail1);
-  return launch_status("mirec_segment_reduce2_f32");
-}
-
-extern "C" int mirec_segment_reduce2_f32(const float* rows, int32_t d, const float* rows1,
-                                         const int32_t* perm, const int32_t* uniq,
-                                         const int32_t* seg, const int32_t* n_uniq_dev, int64_t n,
-                                         float* out, float* out1, void* ws, size_t ws_bytes,
-                                         void* stream) {
-  return reduce2_impl(rows, d, rows1, perm, nullptr, uniq, seg, n_uniq_dev, n, out, out1, ws,
-                      ws_bytes, stream);
-}
-
-extern "C" int mirec_segment_reduce2_pos_seg_f32(const float* rows, int32_t d,
-                                                 const float* rows1, const int32_t* perm,
-                                                 const int32_t* pos_seg, const int32_t* uniq,
-                                                 const int32_t* seg, const int32_t* n_uniq_dev,
-                                                 int64_t n, float* out, float* out1, void* ws,
-                                                 size_t ws_bytes, void* stream) {
-  if (!pos_seg) {
-    set_error("mirec_segment_reduce2_pos_seg_f32: pos_seg is null");
-    return -1;
-  }
-  return reduce2_impl(rows, d, rows1, perm, pos_seg, uniq, seg, n_uniq_dev, n, out, out1, ws,
-                      ws_bytes, stream);
-}
-
-extern "C" int mirec_segment_reduce_pos_seg_f32(const float* rows, int32_t d,
-                                                const int32_t* perm, const int32_t* pos_seg,
-                                                const int32_t* uniq, const int32_t* seg,
-                                                const int32_t* n_uniq_dev, int64_t n, float* out,
-                                                void* ws, size_t ws_bytes, void* stream) {
-  if (n == 0) return 0;
-  if (!rows || !perm || !pos_seg || !uniq || !seg || !n_uniq_dev || !out || d <= 0 ||
-      d > 256 || n < 0 || n > INT32_MAX) {
-    set_error("mirec_segment_reduce_pos_seg_f32: bad arguments (1 <= d <= 256)");
-    return -1;
-  }
-  if (!ws || ws_bytes < mirec_segment_scatter_add_workspace_size(n, d)) {
-    set_error("mirec_segment_reduce_pos_seg_f32: workspace too small");
-    return -1;
-  }
-  const int chunks = (int)((n + scat_chunk(d) - 1) / scat_chunk(d));
-  float* head = (float*)ws;
-  float* tail = head + (int64_t)chunks * d;
-  int32_t* tail_seg = (int32_t*)(tail + (int64_t)chunks * d);
-  hipStream_t st = (hipStream_t)stream;
-  if (d <= 16) {
-    const int64_t gpb = 4 * (64 / 16);
-    hipLaunchKernelGGL((scatter_window_kernel<false>), dim3((unsigned)((chunks + gpb - 1) / gpb)),
-                       dim3(256), 0, st, rows, d, perm, pos_seg, uniq, seg, n_uniq_dev, out, n,
-                       head, tail, tail_seg, chunks, 1, nullptr, nullptr, nullptr, nullptr);
-  } else {
-    const dim3 grd((unsigned)((chunks + 3) / 4));   // four waves (chunks) per workgroup
-#define MIREC_WIDE(MC)                                                                         hipLaunchKernelGGL((scatter_wide_window_kernel<MC>), grd, dim3(256), 0, st, rows, d, perm,                        pos_seg, uniq, seg, n_uniq_dev, out, n, head, tail, tail_seg, chunks, 1)
-    if (d <= 64) MIREC_WIDE(1);
-    else if (d <= 128) MIREC_WIDE(2);
-    else MIREC_WIDE(4);
-#undef MIREC_WIDE
-  }
-  if (chunks > 1)
-    hipLaunchKernelGGL(scatter_fixup_kernel, dim3(fixup_blocks(chunks)), dim3(64 * kFixWaves), 0,
-                       st, d, uniq, seg, tail_seg, out, n, head, tail, chunks, 1);
-  return launch_status("mirec_segment_reduce_pos_seg_f32");
-}
-
-extern "C" int mirec_segment_merge2_f32(const int32_t* uA, const int32_t* nA_dev, int64_t capA,
-                                        const float* rowsA, const int32_t* uB,
-                                        const int32_t* nB_dev, int64_t capB, const float* rowsB,
-                                        int32_t d, int32_t a_pre, int32_t* uniq_out,
-                                        int32_t* n_out_dev, float* rows_out, void* ws,
-                                        size_t ws_bytes, int32_t* status, int64_t n_status,
-                                        void* stream) {
-  const int64_t cap = capA + capB;
-  if (!uA || !nA_dev || !rowsA || !uB || !nB_dev || !rowsB || !uniq_out || !n_out_dev ||
-      !rows_out || !status || capA < 0 || capB < 0 || cap <= 0 || cap >= (int64_t)kOsVal ||
-      d <= 0 || d > 1024) {
-    set_error("mirec_segment_merge2_f32: bad arguments");
-    return -1;
-  }
-  const int64_t tiles = (cap + kMergeTile - 1) / kMergeTile;
-  if (!ws || ws_bytes < (size_t)(2 * cap) * sizeof(int32_t) || n_status < tiles + 1) {
-    set_error("mirec_segment_merge2_f32: workspace (%lld B) or status (%lld words) too small",
-              (long long)(2 * cap * 4), (long long)(tiles + 1));
-    return -1;
-  }
-  int32_t* mk = (int32_t*)ws;
-  int32_t* ref = mk + cap;
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(merge_place_kernel, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, st,
-                     uA, nA_dev, (int)capA, uB, nB_dev, (int)capB, mk, ref);
-  if (d % 4 == 0)
-    hipLaunchKernelGGL(merge_compact_kernel<4>, dim3((unsigned)tiles), dim3(kMergeThreads), 0, st,
-                       mk, ref, nA_dev, nB_dev, rowsA, rowsB, d, a_pre, uniq_out, n_out_dev,
-                       rows_out, (uint32_t*)status, (uint32_t*)status + tiles);
-  else
-    hipLaunchKernelGGL(merge_compact_kernel<1>, dim3((unsigned)tiles), dim3(kMergeThreads), 0, st,
-                       mk, ref, nA_dev, nB_dev, rowsA, rowsB, d, a_pre, uniq_out, n_out_dev,
-                       rows_out, (uint32_t*)status, (uint32_t*)status + tiles);
-  return launch_status("mirec_segment_merge2_f32");
-}
-
-extern "C" int mirec_segment_reduce_f32(const float* rows, int32_t d, const int32_t* perm,
-                                        const int32_t* uniq, const int32_t* seg,
-                                        const int32_t* n_uniq_dev, int64_t n, float* out,
-                                        void* ws, size_t ws_bytes, void* stream) {
-  return scatter_impl(rows, d, perm, uniq, seg, n_uniq_dev, n, out, n, ws, ws_bytes, 1, stream);
 }
 
 // ---------------------------------------------------------------------------

@@ -411,31 +411,42 @@ class Segments:
 
 ONESWEEP_MIN = 8193          # above the single-workgroup LDS sort
 _SORT_STATUS = {}
-_RETIRED = []    # superseded shared scratch buffers: never freed (see _sort_status)
+_RETIRED = []    # superseded shared scratch buffers: never freed (see _grown)
+
+
+def _grown(cache, device, n, make, on_capture=None, floor=1 << 16):
+    """cache[device]: the device's shared buffer of at least n elements — make(size), size
+    at least `floor`, grown on demand. Calls are stream-ordered (the model's stream; a
+    graph's warm-up and capture streams wait for each other): every launch on the stream
+    finishes with the buffer before the next one starts.
+
+    on_capture: while a graph capture is running a missing or too small buffer is not
+    replaced, the caller gets on_capture(n) instead (None: allocate as usual).
+
+    A buffer that is replaced by a larger one stays allocated for the life of the
+    process (_RETIRED): a HIP graph captured earlier holds its pointer and replays against
+    it, and memory handed back to the caching allocator could be reused for other data,
+    so a replay would read garbage look-back words (and scatter outside its outputs). A
+    retired status buffer is still zero (every call leaves it so) and only graphs use
+    it."""
+    key = str(device)
+    buf = cache.get(key)
+    if buf is None or buf.numel() < n:
+        if on_capture is not None and torch.cuda.is_current_stream_capturing():
+            return on_capture(n)
+        if buf is not None:
+            _RETIRED.append(buf)
+        buf = cache[key] = make(max(n, floor))
+    return buf
 
 
 def _sort_status(device, words):
-    """Zeroed look-back / histogram words of the onesweep sort, one buffer per device —
-    every call leaves it zero; calls are stream-ordered (the model's stream; a graph's
-    warm-up and capture streams wait for each other), as for _scatter_ws. None while a
-    graph capture is running and the buffer does not exist yet or is too small (the
-    caller then takes the radix path).
-
-    A buffer that is replaced by a larger one stays allocated for the life of the
-    process: a HIP graph captured earlier holds its pointer and replays against it, and
-    memory handed back to the caching allocator could be reused for other data, so a
-    replay would read garbage look-back words (and scatter outside its outputs). A
-    retired buffer is still zero (every call leaves it so) and only graphs use it."""
-    key = str(device)
-    buf = _SORT_STATUS.get(key)
-    if buf is None or buf.numel() < words:
-        if torch.cuda.is_current_stream_capturing():
-            return None
-        if buf is not None:
-            _RETIRED.append(buf)
-        buf = torch.zeros(max(words, 1 << 16), dtype=torch.int32, device=device)
-        _SORT_STATUS[key] = buf
-    return buf
+    """Zeroed look-back / histogram words of the onesweep sort (every call leaves them
+    zero). None while a graph capture is running and the buffer does not exist yet or is
+    too small (the caller then takes the radix path)."""
+    return _grown(_SORT_STATUS, device, words,
+                  lambda m: torch.zeros(m, dtype=torch.int32, device=device),
+                  on_capture=lambda n: None)
 
 
 def segment_sort(keys: torch.Tensor, key_space: int, segs: Segments | None = None) -> Segments:
@@ -551,16 +562,23 @@ _SCATTER_WS = {}
 
 
 def _scatter_ws(device, nbytes):
-    """Per-device scratch of the chunked scatter (stream-ordered reuse: every
-    launch on the stream finishes with it before the next one starts)."""
-    key = str(device)
-    buf = _SCATTER_WS.get(key)
-    if buf is None or buf.numel() < nbytes:
-        if buf is not None:                  # a captured graph may hold it (_sort_status)
-            _RETIRED.append(buf)
-        buf = torch.empty(max(nbytes, 1 << 16), dtype=torch.uint8, device=device)
-        _SCATTER_WS[key] = buf
-    return buf
+    """Per-device scratch of the chunked scatter."""
+    return _grown(_SCATTER_WS, device, nbytes,
+                  lambda m: torch.empty(m, dtype=torch.uint8, device=device))
+
+
+def _identity_segments(n, uniq, n_uniq, ws, device):
+    """Segments over n compact rows, row u = table row uniq[u]: identity perm / seg /
+    pos_seg (views of the shared iota: no launch per call)."""
+    cap = max(n, 1)
+    ident = Segments.__new__(Segments)
+    ident.n = n
+    iota = _iota(device, cap + 1)
+    ident.perm = iota[:cap]
+    ident.seg = iota[:cap + 1]
+    ident.uniq, ident.n_uniq, ident.ws = uniq, n_uniq, ws
+    ident.pos_seg = ident.perm
+    return ident
 
 
 def segment_scatter_add(rows: torch.Tensor, segs: Segments, dense: torch.Tensor) -> torch.Tensor:
@@ -596,14 +614,7 @@ def segment_reduce(rows: torch.Tensor, segs: Segments):
                                             ptr(segs.seg), ptr(segs.n_uniq), n, ptr(out),
                                             ptr(ws), ws.numel(), stream_handle())
     check(rc, "mirec_segment_reduce_f32")
-    ident = Segments.__new__(Segments)
-    ident.n = n
-    iota = _iota(rows.device, max(n, 1) + 1)       # identity perm / seg: no launch per call
-    ident.perm = iota[:max(n, 1)]
-    ident.seg = iota[:max(n, 1) + 1]
-    ident.uniq, ident.n_uniq, ident.ws = segs.uniq, segs.n_uniq, segs.ws
-    ident.pos_seg = ident.perm
-    return out, ident
+    return out, _identity_segments(n, segs.uniq, segs.n_uniq, segs.ws, rows.device)
 
 
 def segment_merge2(a, b, a_pre=False):
@@ -634,14 +645,7 @@ def segment_merge2(a, b, a_pre=False):
                                         ptr(ws), ws.numel(), ptr(status), status.numel(),
                                         stream_handle())
     check(rc, "mirec_segment_merge2_f32")
-    ident = Segments.__new__(Segments)
-    ident.n = cap
-    iota = _iota(dev, cap + 1)
-    ident.perm = iota[:cap]
-    ident.seg = iota[:cap + 1]
-    ident.uniq, ident.n_uniq, ident.ws = uniq, n_uniq, sa.ws
-    ident.pos_seg = ident.perm
-    return out, ident
+    return out, _identity_segments(cap, uniq, n_uniq, sa.ws, dev)
 
 
 def segment_reduce2(rows: torch.Tensor, rows1: torch.Tensor, segs: Segments):
@@ -665,14 +669,7 @@ def segment_reduce2(rows: torch.Tensor, rows1: torch.Tensor, segs: Segments):
                                              ptr(out), ptr(out1), ptr(ws), ws.numel(),
                                              stream_handle())
     check(rc, "mirec_segment_reduce2_f32")
-    ident = Segments.__new__(Segments)
-    ident.n = n
-    iota = _iota(rows.device, max(n, 1) + 1)
-    ident.perm = iota[:max(n, 1)]
-    ident.seg = iota[:max(n, 1) + 1]
-    ident.uniq, ident.n_uniq, ident.ws = segs.uniq, segs.n_uniq, segs.ws
-    ident.pos_seg = ident.perm
-    return out, out1, ident
+    return out, out1, _identity_segments(n, segs.uniq, segs.n_uniq, segs.ws, rows.device)
 
 
 _IOTA = {}
@@ -680,16 +677,10 @@ _IOTA = {}
 
 def _iota(device, n):
     """0, 1, ..., n-1 as a persistent int32 device tensor (grown on demand; read only).
-    Allocated outside any graph capture the first time a size is needed."""
-    key = str(device)
-    t = _IOTA.get(key)
-    if t is None or t.numel() < n:
-        if torch.cuda.is_current_stream_capturing():   # graph-pool memory: not cached
-            return torch.arange(n, dtype=torch.int32, device=device)
-        if t is not None:                    # a captured graph may hold it (_sort_status)
-            _RETIRED.append(t)
-        t = _IOTA[key] = torch.arange(max(n, 1 << 16), dtype=torch.int32, device=device)
-    return t[:n]
+    Inside a graph capture a size not seen before is graph-pool memory, not cached."""
+    def make(m):
+        return torch.arange(m, dtype=torch.int32, device=device)
+    return _grown(_IOTA, device, n, make, on_capture=make)[:n]
 
 
 # ---------------------------------------------------------------- K5 Adam

@@ -154,7 +154,7 @@ def test_row_sharded_tables_match_replicated(tmp_path, name):
     rows all-to-all'd to owners in global order) against the replicated layout after
     an epoch, on both ranks: bit for bit. Each row's contributions arrive in the same
     order, and the fixed-order reduction cuts them into pieces counted from the row's
-    own first contribution (csrc/segsort.hip scatter_chunks_kernel), so the owner's
+    own first contribution (csrc/segreduce.hip scatter_chunks_kernel), so the owner's
     shorter array gives the same sums as the replicated one."""
     sharded = _two_ranks(tmp_path, name, True, 's')
     replicated = _two_ranks(tmp_path, name, False, 'p')

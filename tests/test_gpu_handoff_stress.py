@@ -4,8 +4,8 @@ consumer L1-warm").
 
 K35's split rows (csrc/step.hip part_store / join: write-through contribution vectors,
 a per-wave drain, one agent-scope add per participant, an acquire on the last adder) and
-the chained / onesweep sorts' status words (csrc/segsort.hip: relaxed agent-scope
-tickets and counts) are each run REPS times back to back, while a streaming copy of
+the chained / onesweep sorts' status words (csrc/segsort.hip, csrc/lookback.h: relaxed
+agent-scope tickets and counts) are each run REPS times back to back, while a streaming copy of
 512 MB runs on another stream and occupies the CUs the launch does not get first (the
 blocks of one launch then start and finish at very different times). The launches
 reuse the same scratch addresses, so a consumer's L1 can hold lines of the previous

@@ -310,6 +310,58 @@ def test_segment_sort_exact(dev, n, key_space):
     assert np.array_equal(segs.seg[:nu + 1].cpu().numpy(), np.r_[starts, n])
 
 
+def _check_sort_batched(dev, keys, batch_n, key_space):
+    """ops.segment_sort_batched (its own workspace sizing) against numpy's stable argsort
+    and np.unique per batch, at the batched layout: perm / uniq at b * batch_n, seg at
+    b * (batch_n + 1), n_uniq[b]."""
+    from recbole_amd import ops
+    n = len(keys)
+    nb = -(-n // batch_n)
+    perm = torch.full((nb * batch_n,), -1, dtype=torch.int32, device=dev)
+    uniq = torch.full((nb * batch_n,), -1, dtype=torch.int32, device=dev)
+    seg = torch.full((nb * (batch_n + 1),), -1, dtype=torch.int32, device=dev)
+    n_uniq = torch.full((nb,), -1, dtype=torch.int32, device=dev)
+    ops.segment_sort_batched(torch.as_tensor(keys, device=dev), batch_n, key_space, perm, uniq,
+                             seg, n_uniq)
+    perm, uniq, seg, n_uniq = (t.cpu().numpy() for t in (perm, uniq, seg, n_uniq))
+    for b in range(nb):
+        kb = keys[b * batch_n:(b + 1) * batch_n]
+        order = np.argsort(kb, kind='stable')
+        u, first = np.unique(kb[order], return_index=True)
+        nu = int(n_uniq[b])
+        assert nu == len(u), b
+        assert np.array_equal(perm[b * batch_n:b * batch_n + len(kb)], order), b
+        assert np.array_equal(uniq[b * batch_n:b * batch_n + nu], u), b
+        assert np.array_equal(seg[b * (batch_n + 1):b * (batch_n + 1) + nu + 1],
+                              np.r_[first, len(kb)]), b
+
+
+@pytest.mark.parametrize('key_space', [1, 33, 5000])
+@pytest.mark.parametrize('n', [8193, 20000])
+def test_segment_sort_large_single_batch_without_status(dev, n, key_space):
+    """One batch past the LDS path with no status buffer (the sort a graph capture takes
+    before one exists): the 5-bit upsweep / scan / downsweep sort. 8,193 keys are 5 tiles
+    of 2,048, the last holding one key; 20,000 leave a ragged last tile. Key space 1: no
+    pass, the permutation is the index column; 33: two passes, the second with one live
+    bit; 5,000: Zipf-hot keys."""
+    rng = np.random.default_rng(n + key_space)
+    keys = (np.minimum(rng.zipf(1.1, n), key_space) - 1).astype(np.int64)
+    _check_sort_batched(dev, keys, n, key_space)
+
+
+@pytest.mark.parametrize('key_space', [7, 5000])
+def test_segment_sort_large_batches_global_kernel(dev, key_space):
+    """Several batches of more than 8,192 keys (a sharded chunk's item keys): one
+    workgroup per batch over global ping-pong buffers, 1-bit splits. Three batches of
+    8,193, the last ragged (100 keys); the first quarter of batch 0 is one key."""
+    batch_n = 8193
+    n = 2 * batch_n + 100
+    rng = np.random.default_rng(n + key_space)
+    keys = rng.integers(0, key_space, n).astype(np.int64)
+    keys[:batch_n // 4] = key_space - 1
+    _check_sort_batched(dev, keys, batch_n, key_space)
+
+
 # ---------------------------------------------------------------- K5 Adam
 @pytest.mark.parametrize('d,wd', [(64, 0.0), (128, 0.0), (32, 0.01)])
 def test_adam_compact_vs_torch_dense_adam(dev, d, wd):
@@ -811,7 +863,7 @@ def test_score_matrix(dev, nq, I, d):
                                            (53_248, 33_000_026, 1), (100_000, 7, 64),
                                            (30_000, 1 << 24, 10)])
 def test_large_segment_sort_and_hot_row_scatter(dev, n, key_space, d):
-    """Device-wide radix path of K2 (n > 8,192) and the chunked scatter: stable
+    """Onesweep sort of K2 (n > 8,192 through ops.segment_sort) and the chunked scatter: stable
     grouping identical to numpy's stable argsort; dense sums vs index_add with
     Zipf-hot rows (one row owns a large share of the contributions)."""
     from recbole_amd import ops
