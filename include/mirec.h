@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define MIREC_ABI_VERSION 25
+#define MIREC_ABI_VERSION 26
 
 int mirec_abi_version(void);
 const char* mirec_last_error(void);
@@ -1555,6 +1555,40 @@ int mirec_cin_wgrad_f32(const float* X0, const float* Xk, int64_t B, int32_t m, 
                         int32_t D, int32_t N, int32_t n_hid, int32_t dir0, const float* dXn,
                         const float* g_pooled, int32_t pool_off, int32_t pool_ld,
                         float* partials, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * K19 — DCN's cross network with the cross slice of the prediction head (csrc/cross.hip;
+ * reference dcn.py:78-99, 101-113). With x0 [B, n] and W, Bv [L, n] row-major:
+ *   s_l = x_l . w_l,   x_{l+1} = x0 s_l + b_l + x_l   (x_0 = x0),   y = x_L . wp
+ * A wave owns a row; no x_l is stored. Built shapes (mirec_cross_shape_ok): 2 <= n <= 1024,
+ * 1 <= L <= 8; anything else is an error. No alignment beyond 4 bytes is asked of x0, xL,
+ * dx0 (or any other operand).
+ *
+ * forward:  writes S [B, L] always; y [B] iff wp != NULL (head mode, y required then); xL
+ *           [B, n] where given (required when wp is NULL: plain mode).
+ * backward: g_L = gy wp + gL; either term is absent when its pointer is NULL (wp and gy
+ *           together), at least one is given. Per row, l = L-1 .. 0: t = g_{l+1} . x0,
+ *           dW_l += t x_l, dB_l += g_{l+1}, dx0 += s_l g_{l+1}, g_l = g_{l+1} + t w_l; then
+ *           dx0 += g_0 and, in head mode, dwp += gy x_L. The x_l are rebuilt from x0, S and
+ *           Bv (x_l = c_l x0 + sum_{k<l} b_k, c_l = 1 + sum_{k<l} s_k). dx0 is written.
+ *           partials [mirec_cross_bwd_splits(B, n, L), mirec_cross_bwd_stride(n, L)]: split
+ *           s's rows' sum of dW (floats [0, L n)), dB ([L n, 2 L n)) and dwp ([2 L n,
+ *           (2L+1) n), zero without head mode); the split of the rows is a function of
+ *           (B, n, L) only; mirec_linear_grad_finish_f32 (bias part NULL) adds the splits
+ *           in order. At most 32 splits whatever B is. stride = round_up((2L+1) n, 4).
+ * Every result is the same bits run to run and for any grid cap. No float atomics.
+ * ------------------------------------------------------------------------- */
+/* mirec_cross_grid_cap(w): as mirec_cin_grid_cap, for K19's two kernels. */
+int32_t mirec_cross_grid_cap(int32_t workgroups);
+int mirec_cross_shape_ok(int32_t n, int32_t L);
+int mirec_cross_fwd_f32(const float* x0, int64_t B, int32_t n, const float* W, const float* Bv,
+                        int32_t L, const float* wp, float* S, float* y, float* xL,
+                        void* stream);
+int32_t mirec_cross_bwd_splits(int64_t B, int32_t n, int32_t L);
+int64_t mirec_cross_bwd_stride(int32_t n, int32_t L);
+int mirec_cross_bwd_f32(const float* x0, int64_t B, int32_t n, const float* W, const float* Bv,
+                        int32_t L, const float* S, const float* wp, const float* gy,
+                        const float* gL, float* dx0, float* partials, void* stream);
 
 #ifdef __cplusplus
 }

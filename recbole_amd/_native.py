@@ -365,9 +365,16 @@ SIGNATURES = {
     "mirec_cin_wgrad_stride": (c_int64, [c_int32, c_int32]),
     "mirec_cin_wgrad_f32": (c_int, [_P, _P, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32,
                                     c_int32, _P, _P, c_int32, c_int32, _P, _P]),
+    "mirec_cross_grid_cap": (c_int32, [c_int32]),
+    "mirec_cross_shape_ok": (c_int, [c_int32, c_int32]),
+    "mirec_cross_fwd_f32": (c_int, [_P, c_int64, c_int32, _P, _P, c_int32, _P, _P, _P, _P, _P]),
+    "mirec_cross_bwd_splits": (c_int32, [c_int64, c_int32, c_int32]),
+    "mirec_cross_bwd_stride": (c_int64, [c_int32, c_int32]),
+    "mirec_cross_bwd_f32": (c_int, [_P, c_int64, c_int32, _P, _P, c_int32, _P, _P, _P, _P, _P,
+                                    _P, _P]),
 }
 
-ABI_VERSION = 25
+ABI_VERSION = 26
 
 
 class NativeError(RuntimeError):

@@ -1,4 +1,5 @@
+from recbole_amd.model.context_aware_recommender.dcn import DCN
 from recbole_amd.model.context_aware_recommender.deepfm import DeepFM
 from recbole_amd.model.context_aware_recommender.xdeepfm import xDeepFM
 
-__all__ = ['DeepFM', 'xDeepFM']
+__all__ = ['DCN', 'DeepFM', 'xDeepFM']

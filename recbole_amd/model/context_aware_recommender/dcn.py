@@ -1,0 +1,211 @@
+"""DCN (mirror of recbole/model/context_aware_recommender/dcn.py:30-122).
+
+y = sigmoid(predict_layer(cat(cross_network(x_0), mlp_layers(x_0)))) with x_0 the field rows
+viewed [B, n = num_feature_field * embedding_size] and the cross network
+x_{l+1} = x_0 (x_l . w_l) + b_l + x_l; nn.BCELoss plus reg_weight * sum_l ||w_l||_2. Same
+class name, config keys, parameter names (cross_layer_w.{i}, cross_layer_b.{i}, mlp_layers,
+predict_layer), construction order and init as the reference, so seeded initial values are
+the reference's and checkpoints are interchangeable.
+
+Where things run on the GPU (fp32):
+  field rows                        K8's first-order form (ContextRecommender.linear_fields);
+                                    its first-order output is not used
+  cross network + the cross slice   K19 (csrc/cross.hip) in head mode: one autograd Function
+  of predict_layer                  (_CrossHeadFn) from x_0, the w_l, the b_l and
+  (cross_kernel: 'fused')           predict_layer.weight[0, :n] to y_cross [B]; one launch
+                                    forward, one backward (+ the fixed-order finish). It saves
+                                    the L scalars s_l = x_l . w_l a row; no x_l, no x_L and no
+                                    cat([cross, deep]) exists
+  DNN tower                         the modules' torch path: Dropout, Linear, BatchNorm1d and
+                                    ReLU are library ops (K10 has no BatchNorm)
+  deep slice of predict_layer       F.linear(deep, predict_layer.weight[:, n:], bias)
+  sigmoid + BCE                     _SigmoidBCEFn (y_cross | y_deep); forward / predict:
+                                    sigmoid_prob
+  regularisation                    one torch norm over the stacked w_l K19 reads (row norms,
+                                    summed); the library path runs RegLoss
+  cross_network(x_0)                K19 in plain mode (x_L is written, the gradient comes in
+                                    as gL)
+
+cross_kernel: 'library', a CPU device, a dtype other than float32 and shapes K19 is not built
+for (mirec_cross_shape_ok: n 2..1024, cross_layer_num 1..8) run cross_library, the
+reference's op sequence, followed by the reference's cat + predict_layer + sigmoid + BCELoss.
+
+first_order_linear exists because the base class builds it; DCN does not use it. In the
+reference its parameters never get a gradient; here they get zero gradients through K8, which
+leave them (Adam, no weight decay) bit-equal to their initial values.
+
+Only the [V, d] token table runs on the deferred Adam schedule, and only at an embedding_size
+the deferred kernels take (4, 16, 32, ...; at the default 10 every table takes the dense
+step). The step runs eagerly (graph_step_safe = False: no capture around K19 was built) on
+one GPU.
+"""
+import torch
+import torch.nn as nn
+from torch.nn.init import constant_, xavier_normal_
+
+from recbole_amd import ops
+from recbole_amd.model.abstract_recommender import ContextRecommender
+from recbole_amd.model.context import _SigmoidBCEFn, sigmoid_prob
+from recbole_amd.model.layers import MLPLayers
+from recbole_amd.model.loss import RegLoss
+
+
+def cross_library(x0, ws, bs):
+    """The reference's op sequence (dcn.py:94-99): per layer a tensordot, two transposes
+    around a broadcast multiply, two adds."""
+    x_l = x0
+    for w, b in zip(ws, bs):
+        xl_w = torch.tensordot(x_l, w, dims=([1], [0]))
+        xl_dot = (x0.transpose(0, 1) * xl_w).transpose(0, 1)
+        x_l = xl_dot + b + x_l
+    return x_l
+
+
+class _CrossHeadFn(torch.autograd.Function):
+    """y_cross [B] = cross_network(x0) . wp through K19 in head mode, W and Bv the stacked
+    [L, n] parameters. Saves x0, the parameters and S [B, L]."""
+
+    @staticmethod
+    def forward(ctx, x0, wp, W, Bv):
+        x0, W, Bv = x0.contiguous(), W.detach().contiguous(), Bv.detach().contiguous()
+        wp = wp.detach().contiguous()
+        S, y, _ = ops.cross_fwd(x0, W, Bv, wp=wp)
+        ctx.save_for_backward(x0, W, Bv, S, wp)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x0, W, Bv, S, wp = ctx.saved_tensors
+        dx0, dW, dB, dwp = ops.cross_bwd(x0, W, Bv, S, wp=wp, gy=gy.contiguous())
+        return dx0, dwp, dW, dB
+
+
+class _CrossFn(torch.autograd.Function):
+    """x_L [B, n] = cross_network(x0) through K19 in plain mode."""
+
+    @staticmethod
+    def forward(ctx, x0, W, Bv):
+        x0, W, Bv = x0.contiguous(), W.detach().contiguous(), Bv.detach().contiguous()
+        S, _, xL = ops.cross_fwd(x0, W, Bv)
+        ctx.save_for_backward(x0, W, Bv, S)
+        return xL
+
+    @staticmethod
+    def backward(ctx, gL):
+        x0, W, Bv, S = ctx.saved_tensors
+        dx0, dW, dB, _ = ops.cross_bwd(x0, W, Bv, S, gL=gL.contiguous())
+        return dx0, dW, dB
+
+
+class DCN(ContextRecommender):
+
+    graph_step_safe = False
+
+    def __init__(self, config, dataset):
+        super().__init__(config, dataset)
+        self.mlp_hidden_size = config['mlp_hidden_size']
+        self.cross_layer_num = config['cross_layer_num']
+        self.reg_weight = config['reg_weight']
+        self.dropout_prob = config['dropout_prob']
+        self.cross_kernel = config['cross_kernel'] if 'cross_kernel' in config else 'fused'
+        if self.cross_kernel not in ('fused', 'library'):
+            raise ValueError(
+                f"cross_kernel must be 'fused' or 'library', got {self.cross_kernel!r}")
+        n = self.num_feature_field * self.embedding_size
+        # all L weights, then all L biases (dcn.py:47-54): the generator's order
+        self.cross_layer_w = nn.ParameterList(
+            nn.Parameter(torch.randn(n).to(self.device)) for _ in range(self.cross_layer_num))
+        self.cross_layer_b = nn.ParameterList(
+            nn.Parameter(torch.zeros(n).to(self.device)) for _ in range(self.cross_layer_num))
+        size_list = [n] + self.mlp_hidden_size
+        self.mlp_layers = MLPLayers(size_list, dropout=self.dropout_prob, bn=True)
+        self.predict_layer = nn.Linear(n + self.mlp_hidden_size[-1], 1)
+        self.reg_loss = RegLoss()
+        self.sigmoid = nn.Sigmoid()
+        self.loss = nn.BCELoss()
+        self.apply(self._init_weights)
+
+    def _init_weights(self, module):
+        if isinstance(module, nn.Embedding):
+            xavier_normal_(module.weight.data)
+        elif isinstance(module, nn.Linear):
+            xavier_normal_(module.weight.data)
+            if module.bias is not None:
+                constant_(module.bias.data, 0)
+
+    def cross_fused_applies(self, x0):
+        """K19 runs when asked for, on the GPU, in fp32, at a built shape."""
+        if self.cross_kernel != 'fused' or not x0.is_cuda or x0.dtype != torch.float32:
+            return False
+        return x0.dim() == 2 and ops.cross_shape_ok(x0.shape[1], self.cross_layer_num)
+
+    def cross_network(self, x_0):
+        """x_L [B, n] (dcn.py:78-99)."""
+        if self.cross_fused_applies(x_0):
+            return _CrossFn.apply(x_0, *self._stacked())
+        return cross_library(x_0, list(self.cross_layer_w), list(self.cross_layer_b))
+
+    def _stacked(self):
+        """(W, Bv) [L, n]: the 2L parameters stacked for K19, two launches a step. Autograd
+        hands each parameter its row of the [L, n] gradient (a contiguous [n] view), which
+        FusedAdam takes as it is."""
+        return torch.stack(list(self.cross_layer_w)), torch.stack(list(self.cross_layer_b))
+
+    def _x0(self, interaction):
+        if self.predict_layer.bias.is_cuda:
+            X0, _ = self.linear_fields(interaction)
+        else:
+            X0, _ = self.linear_fields_torch(interaction)
+        return X0.view(X0.shape[0], -1)
+
+    def _logits(self, x0, W, Bv):
+        """(y_cross [B], y_deep [B, 1]) on the fused path."""
+        n = x0.shape[1]
+        y_cross = _CrossHeadFn.apply(x0, self.predict_layer.weight[0, :n], W, Bv)
+        deep = self.mlp_layers(x0)
+        y_deep = torch.nn.functional.linear(deep, self.predict_layer.weight[:, n:],
+                                            self.predict_layer.bias)
+        return y_cross, y_deep
+
+    def _library_output(self, x0):
+        """dcn.py:106-113."""
+        deep_output = self.mlp_layers(x0)
+        cross_output = cross_library(x0, list(self.cross_layer_w), list(self.cross_layer_b))
+        stack = torch.cat([cross_output, deep_output], dim=-1)
+        return self.sigmoid(self.predict_layer(stack)).squeeze(1)
+
+    def forward(self, interaction):
+        x0 = self._x0(interaction)
+        if self.cross_fused_applies(x0):
+            return sigmoid_prob(*self._logits(x0, *self._stacked()))
+        return self._library_output(x0)
+
+    def calculate_loss(self, interaction):
+        """BCE + reg_weight * sum_l ||w_l||_2 (dcn.py:115-119). On the fused path the norms
+        are the L row norms of the stacked weights K19 reads, one op (the same value)."""
+        label = interaction[self.LABEL]
+        x0 = self._x0(interaction)
+        if self.cross_fused_applies(x0):
+            W, Bv = self._stacked()
+            loss = _SigmoidBCEFn.apply(*self._logits(x0, W, Bv), label)
+            if self.reg_weight:
+                loss = loss + self.reg_weight * W.norm(2, dim=1).sum()
+            return loss
+        loss = self.loss(self._library_output(x0), label.to(x0.dtype))
+        if self.reg_weight:
+            loss = loss + self.reg_weight * self.reg_loss(self.cross_layer_w)
+        return loss
+
+    def predict(self, interaction):
+        return self.forward(interaction)
+
+    def deferred_tables(self):
+        """The [V, d] token table, at a width the deferred kernels take. The [V, 1]
+        first-order table is not offered: DCN never reads it."""
+        from recbole_amd.trainer.optim import FusedAdam
+        if not self.token_field_names:
+            return []
+        T = self.token_embedding_table.embedding.weight
+        if T.shape[1] not in FusedAdam.DEFERRED_WIDTHS:
+            return []
+        return [T]

@@ -16,6 +16,16 @@ class BPRLoss(nn.Module):
         return -torch.log(self.gamma + torch.sigmoid(pos_score - neg_score)).mean()
 
 
+class RegLoss(nn.Module):
+    """Sum of the 2-norms of the given parameters (loss.py:52-67)."""
+
+    def forward(self, parameters):
+        reg_loss = None
+        for W in parameters:
+            reg_loss = W.norm(2) if reg_loss is None else reg_loss + W.norm(2)
+        return reg_loss
+
+
 class EmbLoss(nn.Module):
 
     def __init__(self, norm=2):

@@ -1851,3 +1851,96 @@ def cin_wgrad(X0, Xk, N: int, n_hid: int, dir0: int, dXn, g_pooled, pool_off: in
               "mirec_linear_grad_finish_f32")
     nw = (N * K + 3) // 4 * 4
     return out[:N * K].view(N, K), out[nw:nw + N]
+
+
+# ---------------------------------------------------------------- K19 DCN cross network
+def cross_shape_ok(n: int, L: int) -> bool:
+    """Whether K19 is built for L cross layers over rows of n floats (n 2..1024, L 1..8)."""
+    return lib().mirec_cross_shape_ok(int(n), int(L)) != 0
+
+
+def cross_grid_cap(workgroups: int) -> int:
+    """Cap the workgroups of K19a / K19b at `workgroups` (0: the chip decides; negative: only
+    ask); returns the cap before the call. No output bit depends on it."""
+    return int(lib().mirec_cross_grid_cap(int(workgroups)))
+
+
+def _cross_operands(what, x0, W, Bv, wp=None):
+    _dev(x0, torch.float32, "x0")
+    _dev(W, torch.float32, "W")
+    _dev(Bv, torch.float32, "Bv")
+    if x0.dim() != 2 or W.dim() != 2 or W.shape[1] != x0.shape[1] or Bv.shape != W.shape:
+        raise ValueError(f"{what}: x0 {tuple(x0.shape)}, W {tuple(W.shape)} and Bv "
+                         f"{tuple(Bv.shape)} must be [B, n], [L, n] and [L, n]")
+    B, n = x0.shape
+    L = W.shape[0]
+    if not cross_shape_ok(n, L):
+        raise NativeError(f"{what}: shape n {n}, L {L} not in the built set (n 2..1024, L 1..8)")
+    if wp is not None:
+        _dev(wp, torch.float32, "wp")
+        if wp.shape != (n,):
+            raise ValueError(f"{what}: wp shape {tuple(wp.shape)} != ({n},)")
+    return B, n, L
+
+
+def cross_fwd(x0, W, Bv, wp=None, want_xL=None):
+    """K19a: the cross network x_{l+1} = x0 (x_l . w_l) + b_l + x_l over x0 [B, n] with W, Bv
+    [L, n], no x_l stored. Returns (S [B, L] with s_l = x_l . w_l, y [B] = x_L . wp or None
+    without wp, x_L [B, n] or None). want_xL defaults to `wp is None` (plain mode)."""
+    B, n, L = _cross_operands("cross_fwd", x0, W, Bv, wp)
+    if want_xL is None:
+        want_xL = wp is None
+    if wp is None and not want_xL:
+        raise ValueError("cross_fwd: nothing asked for (neither wp nor x_L)")
+    dev = x0.device
+    S = torch.empty(B, L, dtype=torch.float32, device=dev)
+    y = torch.empty(B, dtype=torch.float32, device=dev) if wp is not None else None
+    xL = torch.empty(B, n, dtype=torch.float32, device=dev) if want_xL else None
+    with timed_launch('cross_fwd'):
+        rc = lib().mirec_cross_fwd_f32(ptr(x0), B, n, ptr(W), ptr(Bv), L, ptr(wp), ptr(S), ptr(y),
+                                       ptr(xL), stream_handle())
+    check(rc, "mirec_cross_fwd_f32")
+    return S, y, xL
+
+
+def cross_bwd(x0, W, Bv, S, wp=None, gy=None, gL=None):
+    """K19b + the finish: the gradients of the cross network for g_L = gy wp + gL (head mode:
+    wp and gy [B] together; plain mode: gL [B, n]; at least one). Returns (dx0 [B, n],
+    dW [L, n], dB [L, n], dwp [n] — zero without head mode), the three weight parts being
+    views of one finished [2L + 1, n] block summed over the rows in a fixed order."""
+    B, n, L = _cross_operands("cross_bwd", x0, W, Bv, wp)
+    _dev(S, torch.float32, "S")
+    if S.shape != (B, L):
+        raise ValueError(f"cross_bwd: S shape {tuple(S.shape)} != {(B, L)}")
+    if (wp is None) != (gy is None):
+        raise ValueError("cross_bwd: wp and gy come together (head mode)")
+    if gy is None and gL is None:
+        raise ValueError("cross_bwd: neither gy nor gL given")
+    if gy is not None:
+        _dev(gy, torch.float32, "gy")
+        if gy.shape != (B,):
+            raise ValueError(f"cross_bwd: gy shape {tuple(gy.shape)} != ({B},)")
+    if gL is not None:
+        _dev(gL, torch.float32, "gL")
+        if gL.shape != (B, n):
+            raise ValueError(f"cross_bwd: gL shape {tuple(gL.shape)} != {(B, n)}")
+    if B == 0:
+        raise ValueError("cross_bwd: no rows")
+    dev = x0.device
+    C = lib().mirec_cross_bwd_splits(B, n, L)
+    stride = lib().mirec_cross_bwd_stride(n, L)
+    P = torch.empty(C, stride, dtype=torch.float32, device=dev)
+    dx0 = torch.empty_like(x0)
+    with timed_launch('cross_bwd'):
+        rc = lib().mirec_cross_bwd_f32(ptr(x0), B, n, ptr(W), ptr(Bv), L, ptr(S), ptr(wp), ptr(gy),
+                                       ptr(gL), ptr(dx0), ptr(P), stream_handle())
+    check(rc, "mirec_cross_bwd_f32")
+    if C == 1:
+        out = P[0]
+    else:
+        out = torch.empty(stride, dtype=torch.float32, device=dev)
+        check(lib().mirec_linear_grad_finish_f32(ptr(P), C, stride, ptr(out), None, 0, 0, None,
+                                                 None, None, stream_handle()),
+              "mirec_linear_grad_finish_f32")
+    block = out[:(2 * L + 1) * n].view(2 * L + 1, n)
+    return dx0, block[:L], block[L:2 * L], block[2 * L]

@@ -47,6 +47,12 @@ C2 headline (bench.py): one JSON line per configuration, 1 GPU.
       against 'library' (einsum + conv1d, z [B, H m, D] in memory) on copies of the same
       weights and batches, alternating windows, peak memory of both, K18's three kernels'
       launch times and MFMA fractions. Not in the default list: --configs xDeepFM (or X4).
+  D4  DCN at the same C4 shape (n = 39 x 16 = 624) with the reference's defaults (6 cross
+      layers, MLP 256-256-256 with BatchNorm, dropout 0.2, reg_weight 2), B = 2,048: the
+      training step with cross_kernel 'fused' (K19, head mode) against 'library' (the
+      reference's op sequence, cat, predict_layer) on copies of the same weights and batches,
+      alternating windows, peak memory of both, K19's two launch times. Not in the default
+      list: --configs DCN (or D4).
 
 Synthetic data (seeded numpy PCG64 / torch generators), random init. Each step is
 the Trainer's generic step: zero_grad -> calculate_loss -> backward -> FusedAdam.
@@ -1262,20 +1268,9 @@ def bench_ngcf(dev, steps, warmup, scale=1.0, B=2048, windows=3):
     }
 
 
-def bench_xdeepfm(dev, steps, warmup, scale=1.0, B=2048, d=16, n_batches=8, windows=3):
-    """X4: one xDeepFM training step (zero_grad, calculate_loss, backward, FusedAdam with the
-    [V, d] token table deferred) at the C4 shape with the reference's defaults
-    (cin_layer_size [100, 100, 100], direct False, MLP 128-128-128-1, dropout 0.2, reg_weight
-    5e-4): cin_kernel 'fused' (K18) against 'library' (the reference's op sequence) on copies
-    of the same initial weights and the same batches. `windows` timed windows of `steps`
-    steps each, the two sides alternating; peak allocated memory of each side's windows; the
-    two steps' loss and CIN weight gradients compared on the first batch with the dropout
-    off. K18's launches are timed by HIP events on their stream over eager steps."""
-    import copy
-    from recbole_amd.config import Config
-    from recbole_amd.data.interaction import Interaction
-    from recbole_amd.model.context_aware_recommender import xDeepFM
-    from recbole_amd.trainer.optim import FusedAdam
+def _criteo_fields(scale):
+    """The C4 shape's fields for a StubDataset: (vocab, types, nums) of 13 float and 26 token
+    fields."""
     from recbole_amd.utils import FeatureType
     vocab = [max(3, int(v * scale)) for v in c4_vocab()]
     types, nums = {'label': FeatureType.FLOAT}, {'label': 1}
@@ -1283,14 +1278,13 @@ def bench_xdeepfm(dev, steps, warmup, scale=1.0, B=2048, d=16, n_batches=8, wind
         types[f'I{j}'], nums[f'I{j}'] = FeatureType.FLOAT, 1
     for j, v in enumerate(vocab):
         types[f'C{j}'], nums[f'C{j}'] = FeatureType.TOKEN, v + 1
-    config = Config(model='xDeepFM', dataset='criteo-synth', config_dict={
-        'embedding_size': d, 'load_col': None, 'state': 'ERROR', 'data_path': ROOT,
-        'cin_kernel': 'fused'})
-    config['device'] = dev
-    torch.manual_seed(2020)
-    model = xDeepFM(config, StubDataset(types, nums)).to(dev)
-    twin = copy.deepcopy(model)
-    twin.cin_kernel = 'library'
+    return vocab, types, nums
+
+
+def _criteo_batches(vocab, B, n_batches, dev):
+    """Seeded batches of that shape on the device: log-normal floats scaled to [0, 1],
+    Zipf(1.1) ids."""
+    from recbole_amd.data.interaction import Interaction
     rng = np.random.default_rng(2020)
     batches = []
     for _ in range(n_batches):
@@ -1302,6 +1296,32 @@ def bench_xdeepfm(dev, steps, warmup, scale=1.0, B=2048, d=16, n_batches=8, wind
         for j, v in enumerate(vocab):
             cols[f'C{j}'] = torch.as_tensor(_zipf_ids(rng, 1.1, B, v))
         batches.append(Interaction(cols).to(dev))
+    return batches
+
+
+def bench_xdeepfm(dev, steps, warmup, scale=1.0, B=2048, d=16, n_batches=8, windows=3):
+    """X4: one xDeepFM training step (zero_grad, calculate_loss, backward, FusedAdam with the
+    [V, d] token table deferred) at the C4 shape with the reference's defaults
+    (cin_layer_size [100, 100, 100], direct False, MLP 128-128-128-1, dropout 0.2, reg_weight
+    5e-4): cin_kernel 'fused' (K18) against 'library' (the reference's op sequence) on copies
+    of the same initial weights and the same batches. `windows` timed windows of `steps`
+    steps each, the two sides alternating; peak allocated memory of each side's windows; the
+    two steps' loss and CIN weight gradients compared on the first batch with the dropout
+    off. K18's launches are timed by HIP events on their stream over eager steps."""
+    import copy
+    from recbole_amd.config import Config
+    from recbole_amd.model.context_aware_recommender import xDeepFM
+    from recbole_amd.trainer.optim import FusedAdam
+    vocab, types, nums = _criteo_fields(scale)
+    config = Config(model='xDeepFM', dataset='criteo-synth', config_dict={
+        'embedding_size': d, 'load_col': None, 'state': 'ERROR', 'data_path': ROOT,
+        'cin_kernel': 'fused'})
+    config['device'] = dev
+    torch.manual_seed(2020)
+    model = xDeepFM(config, StubDataset(types, nums)).to(dev)
+    twin = copy.deepcopy(model)
+    twin.cin_kernel = 'library'
+    batches = _criteo_batches(vocab, B, n_batches, dev)
     m = model.num_feature_field
     assert model.cin_fused_applies(torch.empty(B, m, d, device=dev))
 
@@ -1401,6 +1421,129 @@ def bench_xdeepfm(dev, steps, warmup, scale=1.0, B=2048, d=16, n_batches=8, wind
     }
 
 
+def _set_dropout(mod, p):
+    mod.dropout_prob = p
+    mod.mlp_layers.dropout = p
+    for q in mod.mlp_layers.mlp_layers:
+        if isinstance(q, torch.nn.Dropout):
+            q.p = p
+
+
+def bench_dcn(dev, steps, warmup, scale=1.0, B=2048, d=16, n_batches=8, windows=3):
+    """D4: one DCN training step (zero_grad, calculate_loss, backward, FusedAdam with the
+    [V, d] token table deferred) at the C4 shape with the reference's defaults (6 cross layers,
+    MLP 256-256-256 with BatchNorm, dropout 0.2, reg_weight 2): cross_kernel 'fused' (K19)
+    against 'library' (the reference's op sequence, cat and predict_layer) on copies of the
+    same initial weights and the same batches. `windows` timed windows of `steps` steps each,
+    the two sides alternating; peak allocated memory of each side's windows; the two steps'
+    loss and gradients compared on the first batch with the dropout off. K19's two launches
+    are timed by HIP events on their stream over eager steps."""
+    import copy
+    from recbole_amd.config import Config
+    from recbole_amd.model.context_aware_recommender import DCN
+    from recbole_amd.trainer.optim import FusedAdam
+    vocab, types, nums = _criteo_fields(scale)
+    config = Config(model='DCN', dataset='criteo-synth', config_dict={
+        'embedding_size': d, 'load_col': None, 'state': 'ERROR', 'data_path': ROOT,
+        'cross_kernel': 'fused'})
+    config['device'] = dev
+    torch.manual_seed(2020)
+    model = DCN(config, StubDataset(types, nums)).to(dev)
+    twin = copy.deepcopy(model)
+    twin.cross_kernel = 'library'
+    batches = _criteo_batches(vocab, B, n_batches, dev)
+    n, L = model.num_feature_field * d, model.cross_layer_num
+    assert model.cross_fused_applies(torch.empty(B, n, device=dev))
+    assert not twin.cross_fused_applies(torch.empty(B, n, device=dev))
+
+    # the two steps' outputs on the first batch, dropout off
+    check = {}
+    for side, mod in (('fused', model), ('library', twin)):
+        _set_dropout(mod, 0.0)
+        loss = mod.calculate_loss(batches[0])
+        loss.backward()
+        check[f'loss_{side}'] = loss.item()
+    check['loss_rel_diff'] = abs(check['loss_fused'] - check['loss_library']) / abs(
+        check['loss_library'])
+    check['grad_max_abs_diff'], check['grad_max_abs_library'] = {}, {}
+    for (name, a), (_, b) in zip(model.named_parameters(), twin.named_parameters()):
+        if name.startswith(('cross_layer', 'predict_layer', 'float_embedding_table')):
+            check['grad_max_abs_diff'][name] = float((a.grad - b.grad).abs().max())
+            check['grad_max_abs_library'][name] = float(b.grad.abs().max())
+    for mod in (model, twin):
+        mod.zero_grad(set_to_none=True)
+        _set_dropout(mod, 0.2)
+        for q in mod.mlp_layers.mlp_layers:          # the comparison step's statistics: undone
+            if isinstance(q, torch.nn.BatchNorm1d):
+                q.reset_running_stats()
+
+    opts = []
+    for mod in (model, twin):
+        opt = FusedAdam(mod.parameters(), lr=1e-3)
+        if ADAM_MODE == 'deferred':
+            opt.enable_deferred(mod.deferred_tables())
+        opts.append(opt)
+    it = [0, 0]
+
+    def stepper(side, mod, opt):
+        def step():
+            b = batches[it[side] % n_batches]
+            it[side] += 1
+            opt.zero_grad()
+            mod.calculate_loss(b).backward()
+            opt.step()
+        return step
+
+    step_f, step_l = stepper(0, model, opts[0]), stepper(1, twin, opts[1])
+    tf, tl, peak = [], [], [0, 0]
+    for w in range(windows):
+        for side, (fn, ts) in enumerate(((step_f, tf), (step_l, tl))):
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats(dev)
+            ts.append(_timed(fn, steps, warmup if w == 0 else 1, opts[side]))
+            peak[side] = max(peak[side], torch.cuda.max_memory_allocated(dev))
+    mf, ml = float(np.median(tf)), float(np.median(tl))
+    resident = torch.cuda.memory_allocated(dev)
+    ev = _window_events(step_f, ('cross_fwd', 'cross_bwd'))
+    opts[0].flush()
+    # bytes a launch has to move: x0 in (and dx0 out), the parameters, S, y / gy
+    moved = {'cross_fwd': 4 * (B * n + 2 * L * n + n + B * L + B),
+             'cross_bwd': 4 * (2 * B * n + 2 * L * n + n + B * L + B)}
+    kern = {}
+    for name in ('cross_fwd', 'cross_bwd'):
+        cnt, us = ev[name]
+        kern[name] = {'launches_per_step': cnt, 'launch_us': round(us, 2),
+                      'bytes_per_launch': moved[name], 'bound': 'latency / launch',
+                      'achieved': round(moved[name] / (us * 1e-6) / 1e9, 1), 'unit': 'GB/s',
+                      'timing': 'HIP events around each launch on its stream, 8 eager steps; '
+                                'the finish launch after cross_bwd is outside its pair'}
+    spread = lambda ts: (max(ts) - min(ts)) / float(np.median(ts))
+    V = sum(nums[f'C{j}'] for j in range(26))
+    return {
+        'config': 'D4', 'model': 'DCN', 'metric': 'train samples/s (cross_kernel fused)',
+        'value': round(B / mf, 1), 'unit': 'samples/s', 'ms_per_step': round(mf * 1e3, 3),
+        'ms_per_step_windows': [round(t * 1e3, 3) for t in tf],
+        'window_spread': round(spread(tf), 4),
+        'peak_allocated_MB': round(peak[0] / 1e6, 1),
+        'library': {'ms_per_step': round(ml * 1e3, 3), 'samples_per_s': round(B / ml, 1),
+                    'ms_per_step_windows': [round(t * 1e3, 3) for t in tl],
+                    'window_spread': round(spread(tl), 4),
+                    'peak_allocated_MB': round(peak[1] / 1e6, 1)},
+        'resident_MB_both_models': round(resident / 1e6, 1),
+        'speedup_vs_library': round(ml / mf, 3),
+        'fused_faster_beyond_spread': bool(max(tf) < min(tl)),
+        'k19': kern, 'roofline': kern['cross_bwd'],
+        'windows': windows, 'steps': steps, 'batch': B, 'graph_step': False,
+        'adam_mode': ADAM_MODE, 'outputs_dropout_off': check,
+        'workload': f'DCN Criteo-shape: 13 float + 26 token fields, vocab {V:,} (incl. PADs), '
+                    f'd={d}, n={n}, {L} cross layers, MLP {n}-256-256-256 with BatchNorm, '
+                    f'dropout 0.2, reg_weight 2, BCE, FusedAdam',
+        'dtype': 'fp32', 'data': 'synthetic (Zipf(1.1) ids, log-normal floats, seeded)',
+        'note': f'first measurement: {windows} alternating windows of {steps} steps in one '
+                f'process; no repeat across processes',
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--configs', default='C3,C4,C5')
@@ -1442,6 +1585,8 @@ def main():
             r = bench_bert4rec(dev, args.steps, args.warmup, args.scale)
         elif c in ('X4', 'xDeepFM'):
             r = bench_xdeepfm(dev, args.steps, args.warmup, args.scale)
+        elif c in ('D4', 'DCN'):
+            r = bench_dcn(dev, args.steps, args.warmup, args.scale)
         else:
             raise SystemExit(f'unknown config {c}')
         print(json.dumps(r), flush=True)
