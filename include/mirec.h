@@ -1590,6 +1590,40 @@ int mirec_cross_bwd_f32(const float* x0, int64_t B, int32_t n, const float* W, c
                         int32_t L, const float* S, const float* wp, const float* gy,
                         const float* gL, float* dx0, float* partials, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * K20 — AFM's pairwise-attention layer (csrc/afm.hip; reference afm.py:55-99 and AttLayer,
+ * layers.py:200-225). Per sample, with X [B, F, d] (K8's concat, read as it is), the pairs
+ * p = (i, j), i < j, W [A, d], h [A] and pv [d]:
+ *   z_p = e_i * e_j,  u_p = W z_p,  s_p = h . relu(u_p),  alpha = softmax_p(s),
+ *   v = sum_p alpha_p z_p,  y = dropout_p(v) . pv
+ * A workgroup owns whole samples; nothing of size B x F (F - 1) / 2 exists in either pass.
+ * Built shapes (mirec_afm_shape_ok): F 2..64, d 2..64, A 1..64; anything else is an error.
+ * No alignment beyond 4 bytes is asked of X, dX or any other operand.
+ *
+ * fwd:  y [B]; saved V [B, d] (v before dropout) and ML [B, 2] (the softmax maximum and sum).
+ *       p > 0: the draw of drop.h at element b d + column, keyed by (seed, *counter); the
+ *       counter value used goes to *drawn. p == 0: seed, counter and drawn are ignored.
+ * bwd:  from gy [B]: dX [B, F, d], written once per element, and partials
+ *       [mirec_afm_bwd_splits(B, F, d, A), mirec_afm_bwd_stride(d, A)]: split s's rows' sum of
+ *       dW (floats [0, A d)), dh ([A d, A d + A)) and dpv ([A d + A, A d + A + d)); a split is
+ *       ceil(B / 32) rows; mirec_linear_grad_finish_f32 (bias part NULL) adds the splits in
+ *       order. At most 32 splits whatever B is. stride = round_up(A d + A + d, 4). p > 0
+ *       redraws the forward's keep flags from *drawn and sets *counter = *drawn + 1.
+ * Every result is the same bits run to run and for any grid cap. No float atomics.
+ * ------------------------------------------------------------------------- */
+/* mirec_afm_grid_cap(w): as mirec_cin_grid_cap, for K20's two kernels. */
+int32_t mirec_afm_grid_cap(int32_t workgroups);
+int mirec_afm_shape_ok(int32_t F, int32_t d, int32_t A);
+int mirec_afm_fwd_f32(const float* X, int64_t B, int32_t F, int32_t d, const float* W,
+                      const float* h, int32_t A, const float* pv, float* y, float* V, float* ML,
+                      float p, uint64_t seed, int64_t* counter, int64_t* drawn, void* stream);
+int32_t mirec_afm_bwd_splits(int64_t B, int32_t F, int32_t d, int32_t A);
+int64_t mirec_afm_bwd_stride(int32_t d, int32_t A);
+int mirec_afm_bwd_f32(const float* X, int64_t B, int32_t F, int32_t d, const float* W,
+                      const float* h, int32_t A, const float* pv, const float* V, const float* ML,
+                      const float* gy, float* dX, float* partials, float p, uint64_t seed,
+                      int64_t* drawn, int64_t* counter, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

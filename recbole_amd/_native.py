@@ -372,6 +372,14 @@ SIGNATURES = {
     "mirec_cross_bwd_stride": (c_int64, [c_int32, c_int32]),
     "mirec_cross_bwd_f32": (c_int, [_P, c_int64, c_int32, _P, _P, c_int32, _P, _P, _P, _P, _P,
                                     _P, _P]),
+    "mirec_afm_grid_cap": (c_int32, [c_int32]),
+    "mirec_afm_shape_ok": (c_int, [c_int32, c_int32, c_int32]),
+    "mirec_afm_fwd_f32": (c_int, [_P, c_int64, c_int32, c_int32, _P, _P, c_int32, _P, _P, _P, _P,
+                                  c_float, ctypes.c_uint64, _P, _P, _P]),
+    "mirec_afm_bwd_splits": (c_int32, [c_int64, c_int32, c_int32, c_int32]),
+    "mirec_afm_bwd_stride": (c_int64, [c_int32, c_int32]),
+    "mirec_afm_bwd_f32": (c_int, [_P, c_int64, c_int32, c_int32, _P, _P, c_int32, _P, _P, _P, _P,
+                                  _P, _P, c_float, ctypes.c_uint64, _P, _P, _P]),
 }
 
 ABI_VERSION = 26

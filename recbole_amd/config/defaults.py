@@ -1,6 +1,6 @@
 """Default configuration values, restated as Python data from the reference's
 property files (recbole/properties/overall.yaml, dataset/sample.yaml,
-dataset/ml-100k.yaml, model/{BPR,LightGCN,NGCF,SASRec,GRU4Rec,BERT4Rec,DeepFM,xDeepFM,DCN,NeuMF,
+dataset/ml-100k.yaml, model/{BPR,LightGCN,NGCF,SASRec,GRU4Rec,BERT4Rec,DeepFM,xDeepFM,DCN,AFM,NeuMF,
 MultiDAE,MultiVAE}.yaml,
 quick_start_config/{sequential,context-aware}.yaml)."""
 from recbole_amd.utils.enum_type import ModelType
@@ -77,6 +77,9 @@ MODEL_DEFAULTS = {
     # cross_kernel: the build's key ('fused' = K19, 'library' = the reference's op sequence)
     'DCN': dict(embedding_size=10, mlp_hidden_size=[256, 256, 256], cross_layer_num=6,
                 reg_weight=2, dropout_prob=0.2, cross_kernel='fused'),
+    # afm_kernel: the build's key ('fused' = K20, 'library' = the reference's op sequence)
+    'AFM': dict(embedding_size=10, attention_size=25, dropout_prob=0.3, reg_weight=2,
+                afm_kernel='fused'),
     'NeuMF': dict(mf_embedding_size=64, mlp_embedding_size=64, mlp_hidden_size=[128, 64, 32],
                   dropout_prob=0.0, weight_decay=1e-08, mf_train=True, mlp_train=True,
                   valid_metric='HIT@10', use_pretrain=False, mf_pretrain_path=None,

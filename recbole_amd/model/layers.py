@@ -763,3 +763,22 @@ class SparseDropout(nn.Module):
 
 
 NGCF_SITE = 0x4000                            # + layer: K16a's message dropout (0x3000: K15a)
+AFM_SITE = 0x5000                             # K20a's dropout on the pooled vector
+
+
+class AttLayer(nn.Module):
+    """The attention weights of a [B, M, in_dim] input over its M rows (layers.py:200-225):
+    softmax_M(h . relu(w(x))), shape [B, M]. Torch ops: what AFM's library path and a CPU run
+    use; on the GPU AFM runs K20 (csrc/afm.hip) over the same parameters."""
+
+    def __init__(self, in_dim, att_dim):
+        super().__init__()
+        self.in_dim = in_dim
+        self.att_dim = att_dim
+        self.w = nn.Linear(in_features=in_dim, out_features=att_dim, bias=False)
+        self.h = nn.Parameter(torch.randn(att_dim), requires_grad=True)
+
+    def forward(self, infeatures):
+        att_signal = torch.relu(self.w(infeatures))              # [B, M, att_dim]
+        att_signal = torch.sum(torch.mul(att_signal, self.h), dim=2)
+        return torch.softmax(att_signal, dim=1)                  # [B, M]

@@ -1944,3 +1944,97 @@ def cross_bwd(x0, W, Bv, S, wp=None, gy=None, gL=None):
               "mirec_linear_grad_finish_f32")
     block = out[:(2 * L + 1) * n].view(2 * L + 1, n)
     return dx0, block[:L], block[L:2 * L], block[2 * L]
+
+
+# ---------------------------------------------------------------- K20 AFM pairwise attention
+def afm_shape_ok(F: int, d: int, A: int) -> bool:
+    """Whether K20 is built for F fields of width d and attention size A (F 2..64, d 2..64,
+    A 1..64)."""
+    return lib().mirec_afm_shape_ok(int(F), int(d), int(A)) != 0
+
+
+def afm_grid_cap(workgroups: int) -> int:
+    """Cap the workgroups of K20a / K20b at `workgroups` (0: the chip decides; negative: only
+    ask); returns the cap before the call. No output bit depends on it."""
+    return int(lib().mirec_afm_grid_cap(int(workgroups)))
+
+
+def _afm_operands(what, X, W, h, pv):
+    _dev(X, torch.float32, "X")
+    _dev(W, torch.float32, "W")
+    _dev(h, torch.float32, "h")
+    _dev(pv, torch.float32, "pv")
+    if X.dim() != 3 or W.dim() != 2 or W.shape[1] != X.shape[2] or h.shape != (W.shape[0],) or \
+            pv.shape != (X.shape[2],):
+        raise ValueError(f"{what}: X {tuple(X.shape)}, W {tuple(W.shape)}, h {tuple(h.shape)} and "
+                         f"pv {tuple(pv.shape)} must be [B, F, d], [A, d], [A] and [d]")
+    B, F, d = X.shape
+    A = W.shape[0]
+    if not afm_shape_ok(F, d, A):
+        raise NativeError(f"{what}: shape F {F}, d {d}, A {A} not in the built set (F 2..64, "
+                          f"d 2..64, A 1..64)")
+    return B, F, d, A
+
+
+def _afm_drop(p, rng, drawn):
+    if not p:
+        return 0, None, None
+    seed, counter = rng
+    _dev(counter, torch.int64, "counter")
+    _dev(drawn, torch.int64, "drawn")
+    return seed, counter, drawn
+
+
+def afm_fwd(X, W, h, pv, p: float = 0.0, rng=None, drawn=None):
+    """K20a: y [B] = dropout_p(sum_p alpha_p (e_i * e_j)) . pv with alpha the softmax over the
+    pairs of h . relu(W (e_i * e_j)), from the field rows X [B, F, d]; no pair tensor is
+    stored. Returns (y, V [B, d] — the pooled vector before dropout, ML [B, 2] — the softmax
+    maximum and sum). p > 0: rng = (seed, device int64 counter), drawn = a device int64 word
+    that takes the counter value used (the counter is advanced by the backward)."""
+    B, F, d, A = _afm_operands("afm_fwd", X, W, h, pv)
+    dev = X.device
+    y = torch.empty(B, dtype=torch.float32, device=dev)
+    V = torch.empty(B, d, dtype=torch.float32, device=dev)
+    ML = torch.empty(B, 2, dtype=torch.float32, device=dev)
+    seed, counter, drawn = _afm_drop(p, rng, drawn)
+    with timed_launch('afm_fwd'):
+        rc = lib().mirec_afm_fwd_f32(ptr(X), B, F, d, ptr(W), ptr(h), A, ptr(pv), ptr(y), ptr(V),
+                                     ptr(ML), float(p), seed, ptr(counter), ptr(drawn),
+                                     stream_handle())
+    check(rc, "mirec_afm_fwd_f32")
+    return y, V, ML
+
+
+def afm_bwd(X, W, h, pv, V, ML, gy, p: float = 0.0, rng=None, drawn=None):
+    """K20b + the finish: (dX [B, F, d], dW [A, d], dh [A], dpv [d]) for the upstream gy [B],
+    the three weight parts being views of one finished block summed over the rows in a fixed
+    order. p > 0 redraws the forward's keep flags from `drawn` and sets the counter of rng to
+    drawn + 1."""
+    B, F, d, A = _afm_operands("afm_bwd", X, W, h, pv)
+    _dev(V, torch.float32, "V")
+    _dev(ML, torch.float32, "ML")
+    _dev(gy, torch.float32, "gy")
+    if V.shape != (B, d) or ML.shape != (B, 2) or gy.shape != (B,):
+        raise ValueError(f"afm_bwd: V {tuple(V.shape)}, ML {tuple(ML.shape)} and gy "
+                         f"{tuple(gy.shape)} must be {(B, d)}, {(B, 2)} and ({B},)")
+    if B == 0:
+        raise ValueError("afm_bwd: no rows")
+    dev = X.device
+    C = lib().mirec_afm_bwd_splits(B, F, d, A)
+    stride = lib().mirec_afm_bwd_stride(d, A)
+    P = torch.empty(C, stride, dtype=torch.float32, device=dev)
+    dX = torch.empty_like(X)
+    seed, counter, drawn = _afm_drop(p, rng, drawn)
+    with timed_launch('afm_bwd'):
+        rc = lib().mirec_afm_bwd_f32(ptr(X), B, F, d, ptr(W), ptr(h), A, ptr(pv), ptr(V), ptr(ML),
+                                     ptr(gy), ptr(dX), ptr(P), float(p), seed, ptr(drawn),
+                                     ptr(counter), stream_handle())
+    check(rc, "mirec_afm_bwd_f32")
+    if C == 1:
+        out = P[0]
+    else:
+        out = torch.empty(stride, dtype=torch.float32, device=dev)
+        check(lib().mirec_linear_grad_finish_f32(ptr(P), C, stride, ptr(out), None, 0, 0, None,
+                                                 None, None, stream_handle()),
+              "mirec_linear_grad_finish_f32")
+    return dX, out[:A * d].view(A, d), out[A * d:A * d + A], out[A * d + A:A * d + A + d]

@@ -53,6 +53,12 @@ C2 headline (bench.py): one JSON line per configuration, 1 GPU.
       reference's op sequence, cat, predict_layer) on copies of the same weights and batches,
       alternating windows, peak memory of both, K19's two launch times. Not in the default
       list: --configs DCN (or D4).
+  A4  AFM at the same C4 field shape (F = 39, P = 741 pairs) with the reference's defaults
+      (attention_size 25, dropout 0.3, reg_weight 2) and d = 16, B = 2,048: the training step
+      with afm_kernel 'fused' (K20) against 'library' (the reference's op sequence, the
+      [B, P, d] and [B, P, A] pair tensors in memory) on copies of the same weights and
+      batches, alternating windows, each side's peak memory above what was resident, K20's
+      two launch times. Not in the default list: --configs AFM (or A4).
 
 Synthetic data (seeded numpy PCG64 / torch generators), random init. Each step is
 the Trainer's generic step: zero_grad -> calculate_loss -> backward -> FusedAdam.
@@ -1544,6 +1550,133 @@ def bench_dcn(dev, steps, warmup, scale=1.0, B=2048, d=16, n_batches=8, windows=
     }
 
 
+def bench_afm(dev, steps, warmup, scale=1.0, B=2048, d=16, n_batches=8, windows=3):
+    """A4: one AFM training step (zero_grad, calculate_loss, backward, FusedAdam with the
+    [V, d] and [V, 1] token tables deferred) at the C4 field shape with the reference's
+    defaults (attention_size 25, dropout 0.3, reg_weight 2): afm_kernel 'fused' (K20) against
+    'library' (the reference's op sequence: the [B, P, d] and [B, P, A] pair tensors in
+    memory) on copies of the same initial weights and the same batches. `windows` timed
+    windows of `steps` steps each, the two sides alternating; each side's peak allocated
+    memory above what was resident when its window began (the models, optimizer states and
+    batches); the two steps' loss and gradients compared on the first batch with the dropout
+    off. K20's two launches are timed by HIP events on their stream over eager steps."""
+    import copy
+    from recbole_amd.config import Config
+    from recbole_amd.model.context_aware_recommender import AFM
+    from recbole_amd.trainer.optim import FusedAdam
+    vocab, types, nums = _criteo_fields(scale)
+    config = Config(model='AFM', dataset='criteo-synth', config_dict={
+        'embedding_size': d, 'load_col': None, 'state': 'ERROR', 'data_path': ROOT,
+        'afm_kernel': 'fused'})
+    config['device'] = dev
+    torch.manual_seed(2020)
+    model = AFM(config, StubDataset(types, nums)).to(dev)
+    twin = copy.deepcopy(model)
+    twin.afm_kernel = 'library'
+    batches = _criteo_batches(vocab, B, n_batches, dev)
+    F, A, p_drop = model.num_feature_field, model.attention_size, model.dropout_prob
+    P = F * (F - 1) // 2
+    assert model.afm_fused_applies(torch.empty(B, F, d, device=dev))
+    assert not twin.afm_fused_applies(torch.empty(B, F, d, device=dev))
+
+    def set_dropout(mod, p):
+        mod.dropout_prob = p
+        mod.dropout_layer.p = p
+
+    # the two steps' outputs on the first batch, dropout off
+    check = {}
+    for side, mod in (('fused', model), ('library', twin)):
+        set_dropout(mod, 0.0)
+        loss = mod.calculate_loss(batches[0])
+        loss.backward()
+        check[f'loss_{side}'] = loss.item()
+    check['loss_rel_diff'] = abs(check['loss_fused'] - check['loss_library']) / abs(
+        check['loss_library'])
+    check['grad_max_abs_diff'], check['grad_max_abs_library'] = {}, {}
+    for (name, a), (_, b) in zip(model.named_parameters(), twin.named_parameters()):
+        if name.startswith(('attlayer', 'p', 'float_embedding_table')):
+            check['grad_max_abs_diff'][name] = float((a.grad - b.grad).abs().max())
+            check['grad_max_abs_library'][name] = float(b.grad.abs().max())
+    for mod in (model, twin):
+        mod.zero_grad(set_to_none=True)
+        set_dropout(mod, p_drop)
+
+    opts = []
+    for mod in (model, twin):
+        opt = FusedAdam(mod.parameters(), lr=1e-3)
+        if ADAM_MODE == 'deferred':
+            opt.enable_deferred(mod.deferred_tables())
+        opts.append(opt)
+    it = [0, 0]
+
+    def stepper(side, mod, opt):
+        def step():
+            b = batches[it[side] % n_batches]
+            it[side] += 1
+            opt.zero_grad()
+            mod.calculate_loss(b).backward()
+            opt.step()
+        return step
+
+    step_f, step_l = stepper(0, model, opts[0]), stepper(1, twin, opts[1])
+    tf, tl, peak = [], [], [0, 0]
+    for w in range(windows):
+        for side, (fn, ts) in enumerate(((step_f, tf), (step_l, tl))):
+            torch.cuda.synchronize()
+            opts[side].zero_grad()
+            base = torch.cuda.memory_allocated(dev)
+            torch.cuda.reset_peak_memory_stats(dev)
+            ts.append(_timed(fn, steps, warmup if w == 0 else 1, opts[side]))
+            peak[side] = max(peak[side], torch.cuda.max_memory_allocated(dev) - base)
+    mf, ml = float(np.median(tf)), float(np.median(tl))
+    resident = torch.cuda.memory_allocated(dev)
+    ev = _window_events(step_f, ('afm_fwd', 'afm_bwd'))
+    opts[0].flush()
+    # the MFMA work of a launch as K20 walks it: slabs of 16 pair rows with one left field,
+    # d and A padded to 16; forward one product, backward four (u twice, W^T du, du^T z)
+    slabs = sum((F - 1 - i + 15) // 16 for i in range(F - 1))
+    dp, apad = (d + 15) // 16 * 16, (A + 15) // 16 * 16
+    per = 2 * 16 * dp * apad * slabs * B
+    flops = {'afm_fwd': per, 'afm_bwd': 4 * per}
+    useful = 2 * P * d * A * B
+    kern = {}
+    for name in ('afm_fwd', 'afm_bwd'):
+        cnt, us = ev[name]
+        tf_s = flops[name] / (us * 1e-6) / 1e12
+        kern[name] = {'launches_per_step': cnt, 'launch_us': round(us, 2),
+                      'mfma_flop_per_launch': flops[name],
+                      'useful_flop_per_product': useful,
+                      'achieved': round(tf_s, 2), 'unit': 'TFLOP/s (padded MFMA work)',
+                      'fraction_of_fp32_mfma_peak': round(tf_s / MFMA_F32_PEAK_TFLOPS, 4),
+                      'timing': 'HIP events around each launch on its stream, 8 eager steps; '
+                                'the finish launch after afm_bwd is outside its pair'}
+    spread = lambda ts: (max(ts) - min(ts)) / float(np.median(ts))
+    V = sum(nums[f'C{j}'] for j in range(26))
+    return {
+        'config': 'A4', 'model': 'AFM', 'metric': 'train samples/s (afm_kernel fused)',
+        'value': round(B / mf, 1), 'unit': 'samples/s', 'ms_per_step': round(mf * 1e3, 3),
+        'ms_per_step_windows': [round(t * 1e3, 3) for t in tf],
+        'window_spread': round(spread(tf), 4),
+        'peak_above_resident_MB': round(peak[0] / 1e6, 1),
+        'library': {'ms_per_step': round(ml * 1e3, 3), 'samples_per_s': round(B / ml, 1),
+                    'ms_per_step_windows': [round(t * 1e3, 3) for t in tl],
+                    'window_spread': round(spread(tl), 4),
+                    'peak_above_resident_MB': round(peak[1] / 1e6, 1)},
+        'resident_MB_both_models': round(resident / 1e6, 1),
+        'speedup_vs_library': round(ml / mf, 3),
+        'fused_faster_beyond_spread': bool(max(tf) < min(tl)),
+        'k20': kern, 'roofline': kern['afm_bwd'],
+        'windows': windows, 'steps': steps, 'batch': B, 'graph_step': False,
+        'adam_mode': ADAM_MODE, 'outputs_dropout_off': check,
+        'workload': f'AFM Criteo-shape: 13 float + 26 token fields, vocab {V:,} (incl. PADs), '
+                    f'd={d}, F={F}, P={P} pairs ({slabs} slabs), attention_size {A}, dropout '
+                    f'{p_drop}, reg_weight 2, BCE, FusedAdam',
+        'dtype': 'fp32', 'data': 'synthetic (Zipf(1.1) ids, log-normal floats, seeded)',
+        'note': f'first measurement: {windows} alternating windows of {steps} steps in one '
+                f'process; no repeat across processes',
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--configs', default='C3,C4,C5')
@@ -1587,6 +1720,8 @@ def main():
             r = bench_xdeepfm(dev, args.steps, args.warmup, args.scale)
         elif c in ('D4', 'DCN'):
             r = bench_dcn(dev, args.steps, args.warmup, args.scale)
+        elif c in ('A4', 'AFM'):
+            r = bench_afm(dev, args.steps, args.warmup, args.scale)
         else:
             raise SystemExit(f'unknown config {c}')
         print(json.dumps(r), flush=True)
