@@ -58,6 +58,7 @@
 #include "common.h"
 #include "drop.h"
 #include "mfma.h"
+#include "rowsplit.h"
 
 #include <algorithm>
 
@@ -506,23 +507,13 @@ __global__ __launch_bounds__(64 * WV) void afm_bwd_kernel(
 
 // ---------------------------------------------------------------- host side
 // mirec_afm_grid_cap: most workgroups K20a / K20b launch (0: the samples / splits and the CUs
-// decide). A sample's and a split's results do not depend on which workgroup walks them.
-static int g_afm_grid_cap = 0;
-
-static unsigned afm_grid(int64_t units, int64_t most) {
-  int64_t grid = std::min<int64_t>(units, most);
-  if (g_afm_grid_cap > 0) grid = std::min<int64_t>(grid, g_afm_grid_cap);
-  return (unsigned)std::max<int64_t>(grid, 1);
-}
+// decide)
+static GridCap g_afm_cap;
 
 // K20b's row split, a function of B alone: ceil(B / 32) rows a split
-static void afm_bwd_plan(int64_t B, int64_t* rows, int* splits) {
-  const int64_t r = std::max<int64_t>((B + kAfmMaxSplits - 1) / kAfmMaxSplits, 1);
-  *rows = r;
-  *splits = (int)((B + r - 1) / r);
-}
+static RowSplit afm_bwd_split(int64_t B) { return row_split(B, kAfmMaxSplits, 1, 1); }
 
-static int64_t afm_stride(int d, int A) { return ((int64_t)A * d + A + d + 3) / 4 * 4; }
+static int64_t afm_stride(int d, int A) { return pad4((int64_t)A * d + A + d); }
 
 template <int NU, int NC>
 static int launch_afm_fwd(const float* X, int64_t B, int F, int d, const float* W, const float* h,
@@ -537,7 +528,7 @@ static int launch_afm_fwd(const float* X, int64_t B, int F, int d, const float* 
   int per_cu = 1;
   if (prepare_launch(afm_fwd_kernel<NU, NC>, kAfmThreads, lds_max, cache, &per_cu, what)) return -1;
   const int64_t most = (int64_t)device_cus(current_device()) * per_cu;
-  hipLaunchKernelGGL((afm_fwd_kernel<NU, NC>), dim3(afm_grid(B, most)), dim3(kAfmThreads), lds, st,
+  hipLaunchKernelGGL((afm_fwd_kernel<NU, NC>), dim3(g_afm_cap.grid(B, most)), dim3(kAfmThreads), lds, st,
                      X, B, F, d, W, h, A, pv, y, V, ML, nsl, drop, dr);
   return launch_status(what);
 }
@@ -566,12 +557,10 @@ static int launch_afm_bwd(const float* X, int64_t B, int F, int d, const float* 
   const size_t lds_max = std::min(afm_bwd_lds<NU, NC>(kAfmMaxF, WV), kAfmLdsBudget);
   static int cache[kMaxDev] = {};
   if (prepare_launch(afm_bwd_kernel<NU, NC, WV>, 64 * WV, lds_max, cache, nullptr, what)) return -1;
-  int64_t rows;
-  int splits;
-  afm_bwd_plan(B, &rows, &splits);
-  hipLaunchKernelGGL((afm_bwd_kernel<NU, NC, WV>), dim3(afm_grid(splits, splits)), dim3(64 * WV),
-                     lds, st, X, B, F, d, W, h, A, pv, V, ML, gy, dX, partials, afm_stride(d, A),
-                     rows, splits, nsl, big, drop, dr);
+  const RowSplit sp = afm_bwd_split(B);
+  hipLaunchKernelGGL((afm_bwd_kernel<NU, NC, WV>), dim3(g_afm_cap.grid(sp.splits, sp.splits)),
+                     dim3(64 * WV), lds, st, X, B, F, d, W, h, A, pv, V, ML, gy, dX, partials,
+                     afm_stride(d, A), sp.rows, sp.splits, nsl, big, drop, dr);
   return launch_status(what);
 }
 
@@ -600,13 +589,6 @@ static int afm_shape_error(const char* what, int32_t F, int32_t d, int32_t A) {
   return -1;
 }
 
-static int afm_drop(float p, uint64_t seed, int64_t* counter, int64_t* drawn, DropSite* dr,
-                    const char* what) {
-  *dr = DropSite{0u, 1.f, 0ull, nullptr, nullptr};
-  if (p == 0.f) return 0;
-  return drop_site(p, seed, counter, drawn, dr, what);
-}
-
 }  // namespace mirec
 
 using namespace mirec;
@@ -616,9 +598,7 @@ using namespace mirec;
   MIREC_AFM_TILES(G, 4)
 
 extern "C" int32_t mirec_afm_grid_cap(int32_t workgroups) {
-  const int32_t before = g_afm_grid_cap;
-  if (workgroups >= 0) g_afm_grid_cap = workgroups;
-  return before;
+  return g_afm_cap.exchange(workgroups);
 }
 
 extern "C" int mirec_afm_shape_ok(int32_t F, int32_t d, int32_t A) {
@@ -627,10 +607,7 @@ extern "C" int mirec_afm_shape_ok(int32_t F, int32_t d, int32_t A) {
 
 extern "C" int32_t mirec_afm_bwd_splits(int64_t B, int32_t F, int32_t d, int32_t A) {
   if (B <= 0 || F < 1 || d < 1 || A < 1) return 0;
-  int64_t rows;
-  int splits;
-  afm_bwd_plan(B, &rows, &splits);
-  return splits;
+  return afm_bwd_split(B).splits;
 }
 
 extern "C" int64_t mirec_afm_bwd_stride(int32_t d, int32_t A) {
@@ -649,7 +626,7 @@ extern "C" int mirec_afm_fwd_f32(const float* X, int64_t B, int32_t F, int32_t d
     return -1;
   }
   DropSite dr;
-  if (afm_drop(p, seed, counter, drawn, &dr, what)) return -1;
+  if (drop_site_or_off(p, seed, counter, drawn, &dr, what)) return -1;
   if (B == 0) return 0;
   const int nu = (d + 15) / 16, nc = (A + 15) / 16, drop = p != 0.f;
   hipStream_t st = (hipStream_t)stream;
@@ -673,7 +650,7 @@ extern "C" int mirec_afm_bwd_f32(const float* X, int64_t B, int32_t F, int32_t d
     return -1;
   }
   DropSite dr;
-  if (afm_drop(p, seed, counter, drawn, &dr, what)) return -1;
+  if (drop_site_or_off(p, seed, counter, drawn, &dr, what)) return -1;
   const int nu = (d + 15) / 16, nc = (A + 15) / 16, drop = p != 0.f;
   hipStream_t st = (hipStream_t)stream;
 #define MIREC_AFM(U, C)      \

@@ -57,6 +57,7 @@
 // NK = 16 with NU >= 2 and NK = 12 with NU = 4 (124 - 788 B); no other form does.
 #include "common.h"
 #include "mfma.h"
+#include "rowsplit.h"
 
 #include <algorithm>
 
@@ -429,15 +430,8 @@ __global__ __launch_bounds__(kCinThreads) void cin_wgrad_kernel(
 }
 
 // ---------------------------------------------------------------- host side
-// mirec_cin_grid_cap: most workgroups K18a / K18b launch (0: the CUs decide). A chunk's
-// results do not depend on which workgroup walks it.
-static int g_cin_grid_cap = 0;
-
-static unsigned cin_grid(int64_t passes, int per_cu) {
-  int64_t grid = std::min<int64_t>(passes, (int64_t)device_cus(current_device()) * per_cu);
-  if (g_cin_grid_cap > 0) grid = std::min<int64_t>(grid, g_cin_grid_cap);
-  return (unsigned)std::max<int64_t>(grid, 1);
-}
+// mirec_cin_grid_cap: most workgroups K18a / K18b launch (0: the CUs decide)
+static GridCap g_cin_cap;
 
 // the built tile counts of N: 16 NC >= N
 static int cin_nc(int N) {
@@ -457,9 +451,10 @@ static int launch_cin_fwd(const float* X0, const float* Xk, int64_t B, int m, in
   if (prepare_launch(cin_fwd_kernel<NC, NU>, kCinThreads, lds, cache, &per_cu, what)) return -1;
   const int S = kCinRows / D;
   const int64_t chunks = (B + S - 1) / S;
-  hipLaunchKernelGGL((cin_fwd_kernel<NC, NU>), dim3(cin_grid(chunks, per_cu)), dim3(kCinThreads),
-                     lds, st, X0, Xk, B, m, H, D, W, b, N, n_hid, dir0, Xn, pooled, pool_off,
-                     pool_ld, chunks);
+  const int64_t most = (int64_t)device_cus(current_device()) * per_cu;
+  hipLaunchKernelGGL((cin_fwd_kernel<NC, NU>), dim3(g_cin_cap.grid(chunks, most)),
+                     dim3(kCinThreads), lds, st, X0, Xk, B, m, H, D, W, b, N, n_hid, dir0, Xn,
+                     pooled, pool_off, pool_ld, chunks);
   return launch_status(what);
 }
 
@@ -472,8 +467,10 @@ static int launch_cin_bwd(const float* X0, const float* Xk, int64_t R, int m, in
   int per_cu = 1;
   if (prepare_launch(cin_bwd_kernel<NK, NU>, kCinThreads, lds, cache, &per_cu, what)) return -1;
   const int64_t groups = (R + kCinRows - 1) / kCinRows;
-  hipLaunchKernelGGL((cin_bwd_kernel<NK, NU>), dim3(cin_grid(groups, per_cu)), dim3(kCinThreads),
-                     lds, st, X0, Xk, R, m, H, D, W, g, dXk, dX0, accumulate, groups);
+  const int64_t most = (int64_t)device_cus(current_device()) * per_cu;
+  hipLaunchKernelGGL((cin_bwd_kernel<NK, NU>), dim3(g_cin_cap.grid(groups, most)),
+                     dim3(kCinThreads), lds, st, X0, Xk, R, m, H, D, W, g, dXk, dX0, accumulate,
+                     groups);
   return launch_status(what);
 }
 
@@ -498,14 +495,17 @@ constexpr int kCinWgMaxSplits = 32;
 constexpr int64_t kCinWgMinRows = 256;
 constexpr int kCinWgTarget = 512;         // workgroups wanted
 
-static void cin_wgrad_plan(int64_t R, int m, int H, int64_t* rows, int* splits) {
+static RowSplit cin_wgrad_split(int64_t R, int m, int H) {
   const int units = H * ((m + 15) / 16) + 1;
   const int groups = (units + kCinWaves - 1) / kCinWaves;
-  int want = std::min(kCinWgMaxSplits, std::max(1, kCinWgTarget / groups));
-  int64_t r = (R + want - 1) / want;
-  r = std::max<int64_t>((r + kCinWgRows - 1) / kCinWgRows * kCinWgRows, kCinWgMinRows);
-  *rows = r;
-  *splits = (int)((R + r - 1) / r);
+  const int want = std::min(kCinWgMaxSplits, std::max(1, kCinWgTarget / groups));
+  return row_split(R, want, kCinWgRows, kCinWgMinRows);
+}
+
+static int cin_shape_error(const char* what, int32_t m, int32_t H, int32_t D, int32_t N) {
+  set_error("%s: shape m %d, H %d, D %d, N %d is not built (m 2..64, H 1..256, D 1..64, "
+            "N 2..256)", what, m, H, D, N);
+  return -1;
 }
 
 static bool cin_channels_ok(int N, int n_hid, int dir0) {
@@ -521,9 +521,7 @@ using namespace mirec;
   MIREC_CIN_TILES(F, 4)
 
 extern "C" int32_t mirec_cin_grid_cap(int32_t workgroups) {
-  const int32_t before = g_cin_grid_cap;
-  if (workgroups >= 0) g_cin_grid_cap = workgroups;
-  return before;
+  return g_cin_cap.exchange(workgroups);
 }
 
 extern "C" int mirec_cin_shape_ok(int32_t m, int32_t H, int32_t D, int32_t N) {
@@ -536,11 +534,7 @@ extern "C" int mirec_cin_layer_fwd_f32(const float* X0, const float* Xk, int64_t
                                        float* pooled, int32_t pool_off, int32_t pool_ld,
                                        void* stream) {
   const char* what = "mirec_cin_layer_fwd_f32";
-  if (!mirec_cin_shape_ok(m, H, D, N)) {
-    set_error("%s: shape m %d, H %d, D %d, N %d is not built (m 2..64, H 1..256, D 1..64, "
-              "N 2..256)", what, m, H, D, N);
-    return -1;
-  }
+  if (!mirec_cin_shape_ok(m, H, D, N)) return cin_shape_error(what, m, H, D, N);
   if (B < 0 || !X0 || !Xk || !W || !b || !cin_channels_ok(N, n_hid, dir0) ||
       (n_hid > 0 && !Xn) || (dir0 < N && (!pooled || pool_off < 0 ||
                                           pool_off + (N - dir0) > pool_ld))) {
@@ -563,11 +557,7 @@ static int cin_grad_args(const char* what, int64_t B, int32_t m, int32_t H, int3
                          int32_t n_hid, int32_t dir0, const float* X0, const float* Xk,
                          const float* dXn, const float* g_pooled, int32_t pool_off,
                          int32_t pool_ld, CinGrad* g) {
-  if (!mirec_cin_shape_ok(m, H, D, N)) {
-    set_error("%s: shape m %d, H %d, D %d, N %d is not built (m 2..64, H 1..256, D 1..64, "
-              "N 2..256)", what, m, H, D, N);
-    return -1;
-  }
+  if (!mirec_cin_shape_ok(m, H, D, N)) return cin_shape_error(what, m, H, D, N);
   if (B < 0 || !X0 || !Xk || !cin_channels_ok(N, n_hid, dir0) ||
       (dir0 < N && (!g_pooled || pool_off < 0 || pool_off + (N - dir0) > pool_ld))) {
     set_error("%s: bad arguments", what);
@@ -604,15 +594,12 @@ extern "C" int mirec_cin_layer_bwd_f32(const float* X0, const float* Xk, int64_t
 
 extern "C" int32_t mirec_cin_wgrad_splits(int64_t B, int32_t m, int32_t H, int32_t D) {
   if (B <= 0 || m < 1 || H < 1 || D < 1) return 0;
-  int64_t rows;
-  int splits;
-  cin_wgrad_plan(B * D, m, H, &rows, &splits);
-  return splits;
+  return cin_wgrad_split(B * D, m, H).splits;
 }
 
 extern "C" int64_t mirec_cin_wgrad_stride(int32_t N, int32_t K) {
   if (N < 0 || K < 0) return -1;
-  return ((int64_t)N * K + 3) / 4 * 4 + (N + 3) / 4 * 4;
+  return pad4((int64_t)N * K) + pad4(N);
 }
 
 extern "C" int mirec_cin_wgrad_f32(const float* X0, const float* Xk, int64_t B, int32_t m,
@@ -628,17 +615,15 @@ extern "C" int mirec_cin_wgrad_f32(const float* X0, const float* Xk, int64_t B, 
     set_error("%s: bad arguments", what);
     return -1;
   }
-  int64_t rows;
-  int splits;
-  cin_wgrad_plan(B * D, m, H, &rows, &splits);
+  const RowSplit sp = cin_wgrad_split(B * D, m, H);
   const int64_t stride = mirec_cin_wgrad_stride(N, H * m);
-  const int64_t db_off = ((int64_t)N * H * m + 3) / 4 * 4;
+  const int64_t db_off = pad4((int64_t)N * H * m);
   const int nc = cin_nc(N);
   hipStream_t st = (hipStream_t)stream;
 #define MIREC_CIN(C, U)                                                                      \
   if (nc == C)                                                                               \
-    return launch_cin_wgrad<C>(X0, Xk, B * D, m, H, D, g, rows, splits, partials, stride,     \
-                               db_off, st, what);
+    return launch_cin_wgrad<C>(X0, Xk, B * D, m, H, D, g, sp.rows, sp.splits, partials,      \
+                               stride, db_off, st, what);
   MIREC_CIN_TILES(MIREC_CIN, 0)
 #undef MIREC_CIN
   return -1;

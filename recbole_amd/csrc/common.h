@@ -73,6 +73,27 @@ int prepare_launch(Kern kern, int threads, size_t lds, int (&cache)[kMaxDev], in
   return 0;
 }
 
+// A kernel family's mirec_*_grid_cap: the most workgroups its persistent grids launch (0: the
+// work and the CUs decide). What a row, sample, chunk or split gives does not depend on which
+// workgroup walks it, so a cap changes no bit of any output; the tests cap a grid to make
+// every wave walk several units at a small size. One instance a family: the caps are
+// independent.
+struct GridCap {
+  int cap = 0;
+  // min(units, most, the cap when it is set), at least 1
+  unsigned grid(int64_t units, int64_t most) const {
+    int64_t g = units < most ? units : most;
+    if (cap > 0 && cap < g) g = cap;
+    return (unsigned)(g < 1 ? 1 : g);
+  }
+  // set the cap and return the one before; a negative value only asks
+  int32_t exchange(int32_t workgroups) {
+    const int32_t before = cap;
+    if (workgroups >= 0) cap = workgroups;
+    return before;
+  }
+};
+
 constexpr int kWave = 64;
 
 __device__ __forceinline__ float wave_sum(float x) {

@@ -46,6 +46,7 @@
 // 186 at NK = 1 / 2 / 4 (eight waves), 256 + 58 / 131 / 232 AGPRs at NK = 8 / 12 / 16 (four
 // waves: the 8 NK accumulators and 4 NK row registers do not fit 256 registers a lane).
 #include "common.h"
+#include "rowsplit.h"
 
 #include <algorithm>
 
@@ -380,14 +381,8 @@ __global__ __launch_bounds__(64 * WV) void cross_bwd_kernel(
 
 // ---------------------------------------------------------------- host side
 // mirec_cross_grid_cap: most workgroups K19a / K19b launch (0: the rows / splits and the CUs
-// decide). A row's and a split's results do not depend on which workgroup walks them.
-static int g_cross_grid_cap = 0;
-
-static unsigned cross_grid(int64_t units, int64_t most) {
-  int64_t grid = std::min<int64_t>(units, most);
-  if (g_cross_grid_cap > 0) grid = std::min<int64_t>(grid, g_cross_grid_cap);
-  return (unsigned)std::max<int64_t>(grid, 1);
-}
+// decide)
+static GridCap g_cross_cap;
 
 // the built register tiles of n: 64 NK >= n
 static int cross_nk(int n) {
@@ -397,12 +392,8 @@ static int cross_nk(int n) {
 
 // K19b's row split, a function of B alone: at most kCrossMaxSplits splits, each a multiple of
 // eight rows
-static void cross_bwd_plan(int64_t B, int64_t* rows, int* splits) {
-  int64_t r = (B + kCrossMaxSplits - 1) / kCrossMaxSplits;
-  r = std::max<int64_t>((r + kCrossBwdWaves - 1) / kCrossBwdWaves * kCrossBwdWaves,
-                        kCrossBwdWaves);
-  *rows = r;
-  *splits = (int)((B + r - 1) / r);
+static RowSplit cross_bwd_split(int64_t B) {
+  return row_split(B, kCrossMaxSplits, kCrossBwdWaves, kCrossBwdWaves);
 }
 
 template <int NK>
@@ -419,7 +410,7 @@ static int launch_cross_fwd(const float* x0, int64_t B, int n, const float* W, c
     return -1;
   const int64_t groups = (B + kCrossFwdWaves - 1) / kCrossFwdWaves;
   const int64_t most = (int64_t)device_cus(current_device()) * per_cu;
-  hipLaunchKernelGGL((cross_fwd_kernel<NK>), dim3(cross_grid(groups, most)),
+  hipLaunchKernelGGL((cross_fwd_kernel<NK>), dim3(g_cross_cap.grid(groups, most)),
                      dim3(kCrossFwdThreads), lds, st, x0, B, n, W, Bv, L, wp, S, y, xL, groups);
   return launch_status(what);
 }
@@ -436,12 +427,10 @@ static int launch_cross_bwd(const float* x0, int64_t B, int n, const float* W, c
   static int cache[kMaxDev] = {};
   if (prepare_launch(cross_bwd_kernel<NK, WV>, 64 * WV, lds_max, cache, nullptr, what))
     return -1;
-  int64_t rows;
-  int splits;
-  cross_bwd_plan(B, &rows, &splits);
-  hipLaunchKernelGGL((cross_bwd_kernel<NK, WV>), dim3(cross_grid(splits, splits)),
+  const RowSplit sp = cross_bwd_split(B);
+  hipLaunchKernelGGL((cross_bwd_kernel<NK, WV>), dim3(g_cross_cap.grid(sp.splits, sp.splits)),
                      dim3(64 * WV), lds, st, x0, B, n, W, Bv, L, S, wp, gy, gL, dx0,
-                     partials, mirec_cross_bwd_stride(n, L), rows, splits);
+                     partials, mirec_cross_bwd_stride(n, L), sp.rows, sp.splits);
   return launch_status(what);
 }
 
@@ -458,9 +447,7 @@ using namespace mirec;
 #define MIREC_CROSS_FORMS(F) F(1) F(2) F(4) F(8) F(12) F(16)
 
 extern "C" int32_t mirec_cross_grid_cap(int32_t workgroups) {
-  const int32_t before = g_cross_grid_cap;
-  if (workgroups >= 0) g_cross_grid_cap = workgroups;
-  return before;
+  return g_cross_cap.exchange(workgroups);
 }
 
 extern "C" int mirec_cross_shape_ok(int32_t n, int32_t L) {
@@ -488,15 +475,12 @@ extern "C" int mirec_cross_fwd_f32(const float* x0, int64_t B, int32_t n, const 
 
 extern "C" int32_t mirec_cross_bwd_splits(int64_t B, int32_t n, int32_t L) {
   if (B <= 0 || n < 1 || L < 1) return 0;
-  int64_t rows;
-  int splits;
-  cross_bwd_plan(B, &rows, &splits);
-  return splits;
+  return cross_bwd_split(B).splits;
 }
 
 extern "C" int64_t mirec_cross_bwd_stride(int32_t n, int32_t L) {
   if (n < 0 || L < 0) return -1;
-  return ((int64_t)(2 * L + 1) * n + 3) / 4 * 4;
+  return pad4((int64_t)(2 * L + 1) * n);
 }
 
 extern "C" int mirec_cross_bwd_f32(const float* x0, int64_t B, int32_t n, const float* W,

@@ -82,4 +82,12 @@ inline int drop_site(float p, uint64_t seed, int64_t* counter, int64_t* drawn, D
   return 0;
 }
 
+// p == 0: a switched-off site (scale 1, no words; the kernels' no-dropout forms draw nothing)
+inline int drop_site_or_off(float p, uint64_t seed, int64_t* counter, int64_t* drawn,
+                            DropSite* dr, const char* what) {
+  *dr = DropSite{0u, 1.f, 0ull, nullptr, nullptr};
+  if (p == 0.f) return 0;
+  return drop_site(p, seed, counter, drawn, dr, what);
+}
+
 }  // namespace mirec

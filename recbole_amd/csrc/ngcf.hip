@@ -47,6 +47,7 @@
 #include "common.h"
 #include "drop.h"
 #include "mfma.h"
+#include "rowsplit.h"
 
 #include <algorithm>
 
@@ -312,18 +313,11 @@ __global__ __launch_bounds__(kNgThreads) void ngcf_wgrad_kernel(
 }
 
 // ---------------------------------------------------------------- host side
-// mirec_ngcf_grid_cap: most workgroups K16a / K16b launch (0: the CUs decide). Rows do not
-// depend on which wave walks them, so a cap changes no bit of any output; the tests cap the
-// grid to make every wave walk several slabs at a small N.
-static int g_ng_grid_cap = 0;
+// mirec_ngcf_grid_cap: most workgroups K16a / K16b launch (0: the CUs decide)
+static GridCap g_ng_cap;
 
-static unsigned ng_grid(int64_t M, int per_cu) {
-  const int64_t slabs = (M + 15) / 16;
-  int64_t grid = std::min<int64_t>((slabs + kNgWaves - 1) / kNgWaves,
-                                   (int64_t)device_cus(current_device()) * per_cu);
-  if (g_ng_grid_cap > 0) grid = std::min<int64_t>(grid, g_ng_grid_cap);
-  return (unsigned)grid;
-}
+// workgroups that give every wave one 16-row slab of M rows
+static int64_t ng_groups(int64_t M) { return ((M + 15) / 16 + kNgWaves - 1) / kNgWaves; }
 
 static RowsLd ng_rows(const mirec_rows_ld* a) {
   if (!a) return RowsLd{nullptr, nullptr, 0, 0};
@@ -334,14 +328,6 @@ static RowsLd ng_rows(const mirec_rows_ld* a) {
 static bool ng_rows_ok(const mirec_rows_ld* a, int d) {
   return a && a->lo && a->ld >= d && (a->ld % 4) == 0 && ((uintptr_t)a->lo % 16) == 0 &&
          ((uintptr_t)a->hi % 16) == 0 && (!a->hi || a->split >= 0);
-}
-
-// p == 0: a zeroed site, no dropout (the DROP = false kernels never read it)
-static int ng_drop(float p, uint64_t seed, int64_t* counter, int64_t* drawn, DropSite* dr,
-                   const char* what) {
-  memset(dr, 0, sizeof(*dr));
-  if (p == 0.f) return 0;
-  return drop_site(p, seed, counter, drawn, dr, what);
 }
 
 // K16a / K16b run persistent grids of as many workgroups as a CU holds (prepare_launch: two
@@ -355,8 +341,9 @@ static int launch_fwd(const RowsLd& E, const float* x, int64_t M, const float* W
   int per_cu = 1;
   if (prepare_launch(ngcf_fwd_kernel<DI, DO, DROP>, kNgThreads, lds, cache, &per_cu, what))
     return -1;
-  hipLaunchKernelGGL((ngcf_fwd_kernel<DI, DO, DROP>), dim3(ng_grid(M, per_cu)), dim3(kNgThreads), lds, st,
-                     E, x, M, W1, b1, W2, b2, out, copy, nrm, dr);
+  const int64_t most = (int64_t)device_cus(current_device()) * per_cu;
+  hipLaunchKernelGGL((ngcf_fwd_kernel<DI, DO, DROP>), dim3(g_ng_cap.grid(ng_groups(M), most)),
+                     dim3(kNgThreads), lds, st, E, x, M, W1, b1, W2, b2, out, copy, nrm, dr);
   return launch_status(what);
 }
 
@@ -370,18 +357,23 @@ static int launch_bwd(const RowsLd& G, const RowsLd& En, const float* nrm, int64
   int per_cu = 1;
   if (prepare_launch(ngcf_bwd_kernel<DI, DO, DROP>, kNgThreads, lds, cache, &per_cu, what))
     return -1;
-  hipLaunchKernelGGL((ngcf_bwd_kernel<DI, DO, DROP>), dim3(ng_grid(M, per_cu)), dim3(kNgThreads), lds, st,
-                     G, En, nrm, M, W1, W2, El, x, add, gz, dE, gx, dr);
+  const int64_t most = (int64_t)device_cus(current_device()) * per_cu;
+  hipLaunchKernelGGL((ngcf_bwd_kernel<DI, DO, DROP>), dim3(g_ng_cap.grid(ng_groups(M), most)),
+                     dim3(kNgThreads), lds, st, G, En, nrm, M, W1, W2, El, x, add, gz, dE, gx, dr);
   return launch_status(what);
 }
 
 constexpr int64_t kNgWgradRows = 256;     // least rows per K16c block
-constexpr int64_t kNgWgradMax = 512;      // most partials
+constexpr int kNgWgradMax = 512;          // most partials
 
-static int64_t ng_wgrad_rows(int64_t n) {
-  int64_t rows = (n + kNgWgradMax - 1) / kNgWgradMax;
-  rows = (rows + 15) / 16 * 16;
-  return std::max(rows, kNgWgradRows);
+// K16c's row split: a block's rows are a multiple of the 16 it loads at a time
+static RowSplit ng_wgrad_split(int64_t n) {
+  return row_split(n, kNgWgradMax, 16, kNgWgradRows);
+}
+
+static int ngcf_shape_error(const char* what, int32_t d_in, int32_t d_out) {
+  set_error("%s: widths %d -> %d not in the built set ({64,128}^2)", what, d_in, d_out);
+  return -1;
 }
 
 }  // namespace mirec
@@ -391,9 +383,7 @@ using namespace mirec;
 #define MIREC_NG_WIDTHS(F) F(64, 64) F(64, 128) F(128, 64) F(128, 128)
 
 extern "C" int32_t mirec_ngcf_grid_cap(int32_t workgroups) {
-  const int32_t before = g_ng_grid_cap;
-  if (workgroups >= 0) g_ng_grid_cap = workgroups;
-  return before;
+  return g_ng_cap.exchange(workgroups);
 }
 
 extern "C" int mirec_ngcf_shape_ok(int32_t d_in, int32_t d_out) {
@@ -407,10 +397,7 @@ extern "C" int mirec_ngcf_layer_fwd_f32(const mirec_rows_ld* E, const float* x, 
                                         uint64_t seed, int64_t* counter, int64_t* drawn,
                                         void* stream) {
   const char* what = "mirec_ngcf_layer_fwd_f32";
-  if (!mirec_ngcf_shape_ok(d_in, d_out)) {
-    set_error("%s: widths %d -> %d not in the built set ({64,128}^2)", what, d_in, d_out);
-    return -1;
-  }
+  if (!mirec_ngcf_shape_ok(d_in, d_out)) return ngcf_shape_error(what, d_in, d_out);
   if (n < 0 || !ng_rows_ok(E, d_in) || !ng_rows_ok(out, d_out) || !x || !W1 || !b1 || !W2 || !b2 ||
       !nrm || (((uintptr_t)x | (uintptr_t)W1 | (uintptr_t)W2) & 15)) {
     set_error("%s: bad arguments (16-byte aligned rows, x, W1, W2; ld >= width, ld %% 4 == 0)",
@@ -418,7 +405,7 @@ extern "C" int mirec_ngcf_layer_fwd_f32(const mirec_rows_ld* E, const float* x, 
     return -1;
   }
   DropSite dr;
-  if (ng_drop(p, seed, counter, drawn, &dr, what)) return -1;
+  if (drop_site_or_off(p, seed, counter, drawn, &dr, what)) return -1;
   if (n == 0) return 0;
   const RowsLd e = ng_rows(E), o = ng_rows(out);
   hipStream_t st = (hipStream_t)stream;
@@ -438,10 +425,7 @@ extern "C" int mirec_ngcf_layer_bwd_f32(const mirec_rows_ld* G, const mirec_rows
                                         float* dE, float* gx, float p, uint64_t seed,
                                         int64_t* drawn, int64_t* counter, void* stream) {
   const char* what = "mirec_ngcf_layer_bwd_f32";
-  if (!mirec_ngcf_shape_ok(d_in, d_out)) {
-    set_error("%s: widths %d -> %d not in the built set ({64,128}^2)", what, d_in, d_out);
-    return -1;
-  }
+  if (!mirec_ngcf_shape_ok(d_in, d_out)) return ngcf_shape_error(what, d_in, d_out);
   if (n < 0 || !ng_rows_ok(G, d_out) || !ng_rows_ok(E_next, d_out) || !ng_rows_ok(E, d_in) ||
       (add && add->lo && !ng_rows_ok(add, d_in)) || !nrm || !x || !W1 || !W2 || !gz || !dE || !gx ||
       (((uintptr_t)x | (uintptr_t)W1 | (uintptr_t)W2 | (uintptr_t)gz) & 15)) {
@@ -450,7 +434,7 @@ extern "C" int mirec_ngcf_layer_bwd_f32(const mirec_rows_ld* G, const mirec_rows
     return -1;
   }
   DropSite dr;
-  if (ng_drop(p, seed, counter, drawn, &dr, what)) return -1;
+  if (drop_site_or_off(p, seed, counter, drawn, &dr, what)) return -1;
   if (n == 0) return 0;
   const RowsLd g = ng_rows(G), en = ng_rows(E_next), el = ng_rows(E),
                ad = ng_rows(add && add->lo ? add : nullptr);
@@ -468,29 +452,24 @@ extern "C" int mirec_ngcf_layer_bwd_f32(const mirec_rows_ld* G, const mirec_rows
 
 extern "C" int32_t mirec_ngcf_wgrad_splits(int64_t n) {
   if (n <= 0) return 0;
-  const int64_t rows = ng_wgrad_rows(n);
-  return (int32_t)((n + rows - 1) / rows);
+  return ng_wgrad_split(n).splits;
 }
 
 extern "C" int mirec_ngcf_wgrad_f32(const float* gz, const mirec_rows_ld* E, const float* x,
                                     int64_t n, int32_t d_in, int32_t d_out, float* partials,
                                     void* stream) {
   const char* what = "mirec_ngcf_wgrad_f32";
-  if (!mirec_ngcf_shape_ok(d_in, d_out)) {
-    set_error("%s: widths %d -> %d not in the built set ({64,128}^2)", what, d_in, d_out);
-    return -1;
-  }
+  if (!mirec_ngcf_shape_ok(d_in, d_out)) return ngcf_shape_error(what, d_in, d_out);
   if (n <= 0 || !gz || !x || !partials || !ng_rows_ok(E, d_in)) {
     set_error("%s: bad arguments", what);
     return -1;
   }
   const RowsLd e = ng_rows(E);
-  const int64_t rows = ng_wgrad_rows(n);
-  const unsigned grid = (unsigned)mirec_ngcf_wgrad_splits(n);
+  const RowSplit sp = ng_wgrad_split(n);
 #define MIREC_NG(DI, DO)                                                                     \
   if (d_in == DI && d_out == DO)                                                             \
-    hipLaunchKernelGGL((ngcf_wgrad_kernel<DI, DO>), dim3(grid), dim3(kNgThreads), 0,         \
-                       (hipStream_t)stream, gz, e, x, n, rows, partials);
+    hipLaunchKernelGGL((ngcf_wgrad_kernel<DI, DO>), dim3((unsigned)sp.splits),              \
+                       dim3(kNgThreads), 0, (hipStream_t)stream, gz, e, x, n, sp.rows, partials);
   MIREC_NG_WIDTHS(MIREC_NG)
 #undef MIREC_NG
   return launch_status(what);

@@ -34,7 +34,6 @@ around K20 was built) on one GPU.
 """
 import torch
 import torch.nn as nn
-from torch.nn.init import constant_, xavier_normal_
 
 from recbole_amd import ops
 from recbole_amd.model.abstract_recommender import ContextRecommender
@@ -90,9 +89,7 @@ class AFM(ContextRecommender):
         self.attention_size = config['attention_size']
         self.dropout_prob = config['dropout_prob']
         self.reg_weight = config['reg_weight']
-        self.afm_kernel = config['afm_kernel'] if 'afm_kernel' in config else 'fused'
-        if self.afm_kernel not in ('fused', 'library'):
-            raise ValueError(f"afm_kernel must be 'fused' or 'library', got {self.afm_kernel!r}")
+        self.afm_kernel = self._kernel_choice(config, 'afm_kernel')
         self.num_pair = self.num_feature_field * (self.num_feature_field - 1) / 2
         self.attlayer = AttLayer(self.embedding_size, self.attention_size)
         self.p = nn.Parameter(torch.randn(self.embedding_size), requires_grad=True)
@@ -101,14 +98,6 @@ class AFM(ContextRecommender):
         self.loss = nn.BCELoss()
         self._rng = None
         self.apply(self._init_weights)
-
-    def _init_weights(self, module):
-        if isinstance(module, nn.Embedding):
-            xavier_normal_(module.weight.data)
-        elif isinstance(module, nn.Linear):
-            xavier_normal_(module.weight.data)
-            if module.bias is not None:
-                constant_(module.bias.data, 0)
 
     def afm_fused_applies(self, X):
         """K20 runs when asked for, on the GPU, in fp32, at a built shape."""
@@ -133,10 +122,7 @@ class AFM(ContextRecommender):
 
     def _logits(self, interaction):
         """(first-order term [B], y_afm [B, 1], whether K20 ran)."""
-        if self.p.is_cuda:
-            X, y_first = self.linear_fields(interaction)
-        else:
-            X, y_first = self.linear_fields_torch(interaction)
+        X, y_first = self.first_order_fields(interaction)
         return y_first, self.afm_layer(X), self.afm_fused_applies(X)
 
     def forward(self, interaction):
@@ -163,10 +149,4 @@ class AFM(ContextRecommender):
     def deferred_tables(self):
         """The [V, d] token table and the [V, 1] first-order token weights, read by the same
         rows (as DeepFM), at a width the deferred kernels take."""
-        from recbole_amd.trainer.optim import FusedAdam
-        if not self.token_field_names:
-            return []
-        T = self.token_embedding_table.embedding.weight
-        if T.shape[1] not in FusedAdam.DEFERRED_WIDTHS:
-            return []
-        return [T, self.first_order_linear.token_embedding_table.embedding.weight]
+        return self._deferred_token_tables(with_first_order=True)

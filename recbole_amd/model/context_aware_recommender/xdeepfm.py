@@ -40,7 +40,6 @@ The step runs eagerly (graph_step_safe = False: no capture around K18 was built)
 """
 import torch
 import torch.nn as nn
-from torch.nn.init import constant_, xavier_normal_
 
 from recbole_amd import ops
 from recbole_amd.model.abstract_recommender import ContextRecommender
@@ -128,9 +127,7 @@ class xDeepFM(ContextRecommender):
         self.reg_weight = config['reg_weight']
         self.dropout_prob = config['dropout_prob']
         self.direct = config['direct']
-        self.cin_kernel = config['cin_kernel'] if 'cin_kernel' in config else 'fused'
-        if self.cin_kernel not in ('fused', 'library'):
-            raise ValueError(f"cin_kernel must be 'fused' or 'library', got {self.cin_kernel!r}")
+        self.cin_kernel = self._kernel_choice(config, 'cin_kernel')
         asked = list(config['cin_layer_size'])
         self.cin_layer_size = asked
         if not self.direct:                        # halves go on: even sizes (:48-54)
@@ -158,14 +155,6 @@ class xDeepFM(ContextRecommender):
         self.sigmoid = nn.Sigmoid()
         self.loss = nn.BCELoss()
         self.apply(self._init_weights)
-
-    def _init_weights(self, module):
-        if isinstance(module, nn.Embedding):
-            xavier_normal_(module.weight.data)
-        elif isinstance(module, nn.Linear):
-            xavier_normal_(module.weight.data)
-            if module.bias is not None:
-                constant_(module.bias.data, 0)
 
     def reg_loss(self, parameters):
         """Sum of the 2-norms of the parameters named *weight (:90-100)."""
@@ -213,10 +202,7 @@ class xDeepFM(ContextRecommender):
 
     def _logits(self, interaction):
         """(first_order + cin [B], dnn [B, 1])."""
-        if self.first_order_linear.bias.is_cuda:
-            X0, y_first = self.linear_fields(interaction)
-        else:
-            X0, y_first = self.linear_fields_torch(interaction)
+        X0, y_first = self.first_order_fields(interaction)
         cin = self.cin_linear(self.compressed_interaction_network(X0))
         dnn = self._dnn(X0.view(X0.shape[0], -1))
         return y_first + cin.squeeze(1), dnn
@@ -245,13 +231,4 @@ class xDeepFM(ContextRecommender):
         """The token table [V, d]; the first-order token weights [V, 1] too when no
         regularisation term gives them a dense gradient. K8 catches the [V, 1] rows up beside
         the [V, d] ones, so it is offered only with a [V, d] table the optimizer takes."""
-        from recbole_amd.trainer.optim import FusedAdam
-        if not self.token_field_names:
-            return []
-        T = self.token_embedding_table.embedding.weight
-        if T.shape[1] not in FusedAdam.DEFERRED_WIDTHS:
-            return []
-        tables = [T]
-        if not self.reg_weight:
-            tables.append(self.first_order_linear.token_embedding_table.embedding.weight)
-        return tables
+        return self._deferred_token_tables(with_first_order=not self.reg_weight)

@@ -181,15 +181,8 @@ def _wgrad(x, gy, W, has_b):
     if has_b or C > 1:
         # the C partials' sum and the bias column sum in one launch (two torch
         # reductions before)
-        g2 = g2.contiguous()
-        if has_b:
-            db = torch.empty(n_out, dtype=torch.float32, device=gy.device)
-        scratch = torch.empty(max(lib().mirec_linear_grad_finish_scratch(K, n_out), 2),
-                              dtype=torch.float32, device=gy.device)
-        check(lib().mirec_linear_grad_finish_f32(
-            ptr(P), C, n_out * n_in, ptr(dW), ptr(g2), K, n_out, ptr(db) if db is not None
-            else None, ptr(scratch), ptr(ops.finish_ticket(gy.device, 'linear')),
-            stream_handle()), 'mirec_linear_grad_finish_f32')
+        _, db = ops.linear_grad_finish(P if C > 1 else dW[None],
+                                       g2.contiguous() if has_b else None, dW)
     return dW, db
 
 

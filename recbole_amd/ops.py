@@ -938,6 +938,31 @@ def chunk_finish(loss_k, n: int, stride: int, n_steps: int, denom: float, loss_h
     check(rc, "mirec_chunk_finish")
 
 
+def linear_grad_finish(P, g=None, dW=None):
+    """The fixed-order end of a split weight gradient: (sum over c of the partials P[c], db =
+    the column sum of g [K, n_out] or None without g), one launch. The sum goes to dW where
+    given (dW may be P[0] itself when there is one partial: then only db is formed). One
+    partial and no g: P[0], no launch."""
+    C = P.shape[0]
+    if g is None and C == 1:
+        return P[0], None
+    dev = P.device
+    if dW is None:
+        dW = torch.empty(P.shape[1:], dtype=torch.float32, device=dev)
+    K = n_out = 0
+    db = scratch = ticket = None
+    if g is not None:
+        K, n_out = g.shape
+        db = torch.empty(n_out, dtype=torch.float32, device=dev)
+        scratch = torch.empty(max(lib().mirec_linear_grad_finish_scratch(K, n_out), 2),
+                              dtype=torch.float32, device=dev)
+        ticket = finish_ticket(dev, 'linear')
+    check(lib().mirec_linear_grad_finish_f32(ptr(P), C, dW.numel(), ptr(dW), ptr(g), K, n_out,
+                                             ptr(db), ptr(scratch), ptr(ticket), stream_handle()),
+          "mirec_linear_grad_finish_f32")
+    return dW, db
+
+
 def step_finish(loss_k, denom: float, loss_hist, step_idx):
     _dev(loss_k, torch.float32, "loss_k")
     _dev(step_idx, torch.int32, "step_idx")
@@ -1617,6 +1642,17 @@ def _rows_ld(t, d: int, name: str):
     return RowsLd(ptr(t), None, t.shape[0], t.stride(0)), t.shape[0]
 
 
+def _drop_args(p, rng, drawn):
+    """(seed, counter, drawn) of a dropout site as the kernels take them: p > 0 needs rng =
+    (seed, device int64 counter) and the device int64 word `drawn`; p == 0 passes no words."""
+    if not p:
+        return 0, None, None
+    seed, counter = rng
+    _dev(counter, torch.int64, "counter")
+    _dev(drawn, torch.int64, "drawn")
+    return seed, counter, drawn
+
+
 def ngcf_shape_ok(d_in: int, d_out: int) -> bool:
     """Whether K16 is built for a layer d_in -> d_out ({64, 128}^2)."""
     return lib().mirec_ngcf_shape_ok(int(d_in), int(d_out)) != 0
@@ -1663,14 +1699,10 @@ def ngcf_layer_fwd(E, x, W1, b1, W2, b2, out, copy=None, p: float = 0.0, rng=Non
         if copy.shape != (n, d_out):
             raise ValueError(f"ngcf_layer_fwd: copy shape {tuple(copy.shape)} != {(n, d_out)}")
     nrm = torch.empty(n, dtype=torch.float32, device=x.device)
-    seed, counter = (0, None) if not p else rng
-    if p:
-        _dev(counter, torch.int64, "counter")
-        _dev(drawn, torch.int64, "drawn")
+    seed, counter, drawn = _drop_args(p, rng, drawn)
     rc = lib().mirec_ngcf_layer_fwd_f32(ctypes.byref(Er), ptr(x), n, d_in, d_out, ptr(W1), ptr(b1),
                                         ptr(W2), ptr(b2), ctypes.byref(Or), ptr(copy), ptr(nrm),
-                                        float(p), seed, ptr(counter), ptr(drawn) if p else None,
-                                        stream_handle())
+                                        float(p), seed, ptr(counter), ptr(drawn), stream_handle())
     check(rc, "mirec_ngcf_layer_fwd_f32")
     return nrm
 
@@ -1694,15 +1726,11 @@ def ngcf_layer_bwd(G, E_next, nrm, W1, W2, E, x, add=None, p: float = 0.0, rng=N
     gz = torch.empty(n, d_out, dtype=torch.float32, device=dev)
     dE = torch.empty(n, d_in, dtype=torch.float32, device=dev)
     gx = torch.empty(n, d_in, dtype=torch.float32, device=dev)
-    seed, counter = (0, None) if not p else rng
-    if p:
-        _dev(counter, torch.int64, "counter")
-        _dev(drawn, torch.int64, "drawn")
+    seed, counter, drawn = _drop_args(p, rng, drawn)
     rc = lib().mirec_ngcf_layer_bwd_f32(ctypes.byref(Gr), ctypes.byref(Nr), ptr(nrm), n, d_in,
                                         d_out, ptr(W1), ptr(W2), ctypes.byref(Er), ptr(x),
                                         ctypes.byref(Ar), ptr(gz), ptr(dE), ptr(gx), float(p),
-                                        seed, ptr(drawn) if p else None, ptr(counter),
-                                        stream_handle())
+                                        seed, ptr(drawn), ptr(counter), stream_handle())
     check(rc, "mirec_ngcf_layer_bwd_f32")
     return gz, dE, gx
 
@@ -1724,14 +1752,7 @@ def ngcf_wgrad(gz, E, x, d_in: int):
     P = torch.empty(C, d_out, 2 * d_in, dtype=torch.float32, device=dev)
     check(lib().mirec_ngcf_wgrad_f32(ptr(gz), ctypes.byref(Er), ptr(x), n, d_in, d_out, ptr(P),
                                      stream_handle()), "mirec_ngcf_wgrad_f32")
-    dW = torch.empty(d_out, 2 * d_in, dtype=torch.float32, device=dev)
-    db = torch.empty(d_out, dtype=torch.float32, device=dev)
-    scratch = torch.empty(max(lib().mirec_linear_grad_finish_scratch(n, d_out), 2),
-                          dtype=torch.float32, device=dev)
-    check(lib().mirec_linear_grad_finish_f32(ptr(P), C, d_out * 2 * d_in, ptr(dW), ptr(gz), n,
-                                             d_out, ptr(db), ptr(scratch),
-                                             ptr(finish_ticket(dev, 'linear')), stream_handle()),
-          "mirec_linear_grad_finish_f32")
+    dW, db = linear_grad_finish(P, gz)
     return dW[:, :d_in].contiguous(), dW[:, d_in:].contiguous(), db
 
 
@@ -1842,13 +1863,7 @@ def cin_wgrad(X0, Xk, N: int, n_hid: int, dir0: int, dXn, g_pooled, pool_off: in
         rc = lib().mirec_cin_wgrad_f32(ptr(X0), ptr(Xk), B, m, H, D, N, n_hid, dir0, ptr(dXn),
                                        ptr(g_pooled), pool_off, ld, ptr(P), stream_handle())
     check(rc, "mirec_cin_wgrad_f32")
-    if C == 1:
-        out = P[0]
-    else:
-        out = torch.empty(stride, dtype=torch.float32, device=dev)
-        check(lib().mirec_linear_grad_finish_f32(ptr(P), C, stride, ptr(out), None, 0, 0, None,
-                                                 None, None, stream_handle()),
-              "mirec_linear_grad_finish_f32")
+    out, _ = linear_grad_finish(P)
     nw = (N * K + 3) // 4 * 4
     return out[:N * K].view(N, K), out[nw:nw + N]
 
@@ -1935,13 +1950,7 @@ def cross_bwd(x0, W, Bv, S, wp=None, gy=None, gL=None):
         rc = lib().mirec_cross_bwd_f32(ptr(x0), B, n, ptr(W), ptr(Bv), L, ptr(S), ptr(wp), ptr(gy),
                                        ptr(gL), ptr(dx0), ptr(P), stream_handle())
     check(rc, "mirec_cross_bwd_f32")
-    if C == 1:
-        out = P[0]
-    else:
-        out = torch.empty(stride, dtype=torch.float32, device=dev)
-        check(lib().mirec_linear_grad_finish_f32(ptr(P), C, stride, ptr(out), None, 0, 0, None,
-                                                 None, None, stream_handle()),
-              "mirec_linear_grad_finish_f32")
+    out, _ = linear_grad_finish(P)
     block = out[:(2 * L + 1) * n].view(2 * L + 1, n)
     return dx0, block[:L], block[L:2 * L], block[2 * L]
 
@@ -1976,15 +1985,6 @@ def _afm_operands(what, X, W, h, pv):
     return B, F, d, A
 
 
-def _afm_drop(p, rng, drawn):
-    if not p:
-        return 0, None, None
-    seed, counter = rng
-    _dev(counter, torch.int64, "counter")
-    _dev(drawn, torch.int64, "drawn")
-    return seed, counter, drawn
-
-
 def afm_fwd(X, W, h, pv, p: float = 0.0, rng=None, drawn=None):
     """K20a: y [B] = dropout_p(sum_p alpha_p (e_i * e_j)) . pv with alpha the softmax over the
     pairs of h . relu(W (e_i * e_j)), from the field rows X [B, F, d]; no pair tensor is
@@ -1996,7 +1996,7 @@ def afm_fwd(X, W, h, pv, p: float = 0.0, rng=None, drawn=None):
     y = torch.empty(B, dtype=torch.float32, device=dev)
     V = torch.empty(B, d, dtype=torch.float32, device=dev)
     ML = torch.empty(B, 2, dtype=torch.float32, device=dev)
-    seed, counter, drawn = _afm_drop(p, rng, drawn)
+    seed, counter, drawn = _drop_args(p, rng, drawn)
     with timed_launch('afm_fwd'):
         rc = lib().mirec_afm_fwd_f32(ptr(X), B, F, d, ptr(W), ptr(h), A, ptr(pv), ptr(y), ptr(V),
                                      ptr(ML), float(p), seed, ptr(counter), ptr(drawn),
@@ -2024,17 +2024,11 @@ def afm_bwd(X, W, h, pv, V, ML, gy, p: float = 0.0, rng=None, drawn=None):
     stride = lib().mirec_afm_bwd_stride(d, A)
     P = torch.empty(C, stride, dtype=torch.float32, device=dev)
     dX = torch.empty_like(X)
-    seed, counter, drawn = _afm_drop(p, rng, drawn)
+    seed, counter, drawn = _drop_args(p, rng, drawn)
     with timed_launch('afm_bwd'):
         rc = lib().mirec_afm_bwd_f32(ptr(X), B, F, d, ptr(W), ptr(h), A, ptr(pv), ptr(V), ptr(ML),
                                      ptr(gy), ptr(dX), ptr(P), float(p), seed, ptr(drawn),
                                      ptr(counter), stream_handle())
     check(rc, "mirec_afm_bwd_f32")
-    if C == 1:
-        out = P[0]
-    else:
-        out = torch.empty(stride, dtype=torch.float32, device=dev)
-        check(lib().mirec_linear_grad_finish_f32(ptr(P), C, stride, ptr(out), None, 0, 0, None,
-                                                 None, None, stream_handle()),
-              "mirec_linear_grad_finish_f32")
+    out, _ = linear_grad_finish(P)
     return dX, out[:A * d].view(A, d), out[A * d:A * d + A], out[A * d + A:A * d + A + d]
